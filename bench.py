@@ -8,10 +8,28 @@ left in HBM (device buffers).  On N > 1 GPUs the panorama is split into N
 azimuth sectors (image-column ranges), one per rank, and the strips are gathered
 to rank 0 over RCCL inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--full] [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for what each field
 means and how `roofline` is derived.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`,
+`ms_per_step` and the `roofline` of the timed steps).  --full adds everything
+else the line can carry, each with runs of its own: the parity gates of the
+last timed panorama (oracle/ and the reference's llvmpipe hashes), the latency
+of one panorama, the same viewpoint from the vertex cache, zfar = 40 km, the
+host-inclusive path, another context's init, the CPU baseline, the scenes and,
+for N > 1, the other gather mode and the gathered panorama against the
+single-GPU render.  The --no-* switches trim a --full run.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy
+files: image.npy (H, W, 3: B, G, R) and ranges.npy (H, W) where both fit in
+48 MB, otherwise image_sample.npy (n, 3) and ranges_sample.npy (n,) at a fixed,
+seeded sample of pixels (the sorted unique flat indices of
+numpy.random.default_rng(DUMP_SEED).integers(0, H*W, DUMP_SAMPLE)); always
+the float64 sums of every pixel per row and per column (image_row_sums.npy,
+image_col_sums.npy, ranges_row_sums.npy, ranges_col_sums.npy).  The inputs
+(synthetic DEM, viewpoint, view) depend on the arguments alone.
 """
 import argparse
 import json
@@ -36,6 +54,9 @@ CONFIGS = {
 LAT, LON = 34.4137, -117.5621
 ZNEAR = 100.0
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s HBM3E
+DUMP_FULL_BYTES = 48 << 20     # --dump-outputs: whole arrays up to this size, a sample of pixels beyond it
+DUMP_SAMPLE = 2_000_000        # draws of the sample (with replacement; the unique ones are kept)
+DUMP_SEED = 20260101
 
 
 def parse():
@@ -47,6 +68,12 @@ def parse():
     ap.add_argument("--zfar", type=float, default=600000.0,
                     help="far clip range in m; 600 km keeps every triangle of the mosaic live")
     ap.add_argument("--raster", type=int, default=0, help="HZ_RASTER_* (0 auto, 1 scatter, 2 march)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks (parity gates, single-panorama latency, vertex cache, zfar = 40 km, "
+                         "host-inclusive path, init, CPU baseline, scenes; N > 1: the other gather mode, the gathered panorama "
+                         "against the single-GPU render); off: only the timed steps the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (BGR image and float32 ranges) as float32/float64 .npy files to DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (zfar = 40 km, the scenes)")
     ap.add_argument("--no-host", action="store_true", help="skip the host-inclusive measurement (results into host memory)")
@@ -75,6 +102,32 @@ def parse():
     return ap.parse_args()
 
 
+def dump_outputs(out_dir, d_img, d_rng):
+    """--dump-outputs: the BGR image and the float32 ranges of the last timed panorama as float32 / float64 .npy files
+    (whole where they fit in DUMP_FULL_BYTES, else a fixed seeded sample of pixels; the row and column sums always)"""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    img = d_img.cpu().numpy()
+    rng = d_rng.cpu().numpy()
+    H, W = rng.shape
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    if 16 * H * W <= DUMP_FULL_BYTES:
+        out["image"] = img.astype(np.float32)
+        out["ranges"] = rng.astype(np.float32)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, H * W, DUMP_SAMPLE))
+        out["image_sample"] = img.reshape(-1, 3)[idx].astype(np.float32)
+        out["ranges_sample"] = rng.reshape(-1)[idx].astype(np.float32)
+    out["image_row_sums"] = img.sum(axis=1, dtype=np.float64)
+    out["image_col_sums"] = img.sum(axis=0, dtype=np.float64)
+    out["ranges_row_sums"] = rng.sum(axis=1, dtype=np.float64)
+    out["ranges_col_sums"] = rng.sum(axis=0, dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     # never a hang: whatever blocks (a collective that never completes, a stream behind it), the process says where and
@@ -99,6 +152,9 @@ def main():
             sys.exit(subprocess.call(cmd, env=env))
         args.gpus = world
 
+    if not args.full:
+        # a plain run: set-up, warm-up, the K timed steps and the line - the side measurements and checks are --full's
+        args.no_cpu_baseline = args.no_extra = args.no_host = args.no_scenes = True
     if args.config == "cfg5":
         # 3.1 G triangles: the CPU oracle needs half a minute per render, the results are 1.9 GB - the side measurements are cfg3's
         args.no_cpu_baseline = args.no_host = args.no_scenes = True
@@ -335,6 +391,7 @@ def main():
                 state["wire_words"] = S["rs"].words
                 S["rs"].run(n)
         state["converted"] += sum(1 for i in range(first, first + n) if (i % world if S["rotate"] else 0) == rank)
+        state["last_dst"] = (S["rs"].next - 1) % world if S["rotate"] else 0
 
     def convert(bins):
         """rank 0: the strips of one panorama -> the full-width outputs, on the library's conversion
@@ -383,6 +440,7 @@ def main():
         slot = state["k"] % NBUF
         dst = state["k"] % world if S["rotate"] else 0      # the rank that gathers and converts this panorama
         state["k"] += 1
+        state["last_dst"] = dst
         if not multi:
             # no wait in between: the library overlaps the readback conversion and the clear of
             # panorama k (its second stream) with the rasterisation of panorama k+1
@@ -509,7 +567,9 @@ def main():
     # switched off for `value` and measured beside it ("same_viewpoint").
     h.set_options(vertex_cache=0)
     dt, kern = timed(args.zfar, args.steps, args.warmup)
-    verified = verify()
+    if args.dump_outputs and state.get("last_dst", 0) == rank:
+        dump_outputs(args.dump_outputs, d_img, d_rng)      # the rank that holds the last timed panorama
+    verified = verify() if args.full else None
 
     # "parity gates recorded with every timing".  The panorama that was just timed - the LAST of
     # the K queued back to back, i.e. drawn by the kernels of a series: second round with coarse depth (k_march<false,
@@ -543,12 +603,12 @@ def main():
         return {"img": img, "rng": d_rng.cpu().numpy(), "plan": plan,
                 "bgr_sha_is_llvmpipe": (hashlib.sha256(img.tobytes()).hexdigest() == g["bgr_sha256"]) if g else None}
 
-    last = keep_last(args.zfar)
+    last = keep_last(args.zfar) if args.full else None
 
     # What ONE panorama costs (N = 1): the series above is K panoramas queued back to back, whose rounds and conversions
     # overlap; a caller that waits for each render sees this instead.  Outputs left in HBM, like `value`.
     single_latency = None
-    if world == 1 and not args.exchange_anyway:
+    if args.full and world == 1 and not args.exchange_anyway:
         ts1 = []
         for k in range(8):
             drain()
@@ -584,7 +644,7 @@ def main():
     # strips" to ONE place, every panorama assembled on rank 0), and what ONE panorama takes at this N from the call to
     # the assembled panorama on rank 0 - a draw that is waited for, its gather, its conversion, nothing to overlap with.
     multi_extra = {}
-    if world > 1 or args.exchange_anyway:
+    if args.full and (world > 1 or args.exchange_anyway):
         def relayout():
             cos_lat = float(np.cos(np.radians(LAT)))
             apply_layout(balanced_layout(azimuth_density(W, -180.0, 180.0, cos_lat, floor=0.1), world, S["weights"]))

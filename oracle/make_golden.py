@@ -89,15 +89,33 @@ def vertex_fixture(name, R, W, H, az0, az1, lat=LAT, lon=LON, **kw):
     print(f"vertex_{name}.npz: {m.shape[0]}^2 vertices")
 
 
-def render_fixture(name, R, W, H, az0, az1, lat=LAT, lon=LON, keep_depth=True, rough=False, **kw):
+def savez_lzma(path, **arrays):
+    """np.savez_compressed with LZMA instead of deflate (np.load reads either): keeps a fixture under 1 MiB"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            z.writestr(k + ".npy", buf.getvalue())
+
+
+def render_fixture(name, R, W, H, az0, az1, lat=LAT, lon=LON, keep_depth=True, rough=False, keep_mosaic=True, **kw):
+    """keep_mosaic=False: the fixture holds the mosaic's SHA-256 and radius instead of the mosaic
+    (tests/hzutil.py: load_render_fixture rebuilds it from the synthetic tiles)"""
+    import hashlib
     d = hzutil.dem_dir_for(LAT, LON, R, rough=rough)
     od = oracle.Dem(LAT, LON, d, radius_cells=R)
     m = od.mosaic()
     v = od.view(lat, lon, W, H, az0, az1, **kw)
     g = glsl_run.render(m, v, W, H)
     extra = {"depth": g["depth"]} if keep_depth else {}
-    np.savez_compressed(os.path.join(OUT, f"render_{name}.npz"), mosaic=m, W=np.int32(W), H=np.int32(H),
-                        bgr=g["bgr"], z24=g["z24"], **extra, **view_arrays(v))
+    dem = {"mosaic": m} if keep_mosaic else {}
+    rest = {} if keep_mosaic else {"mosaic_sha256": np.array(hashlib.sha256(np.ascontiguousarray(m).tobytes()).hexdigest()),
+                                   "mosaic_R": np.int32(R)}
+    assert keep_mosaic or not rough
+    savez_lzma(os.path.join(OUT, f"render_{name}.npz"), **dem, W=np.int32(W), H=np.int32(H),
+               bgr=g["bgr"], z24=g["z24"], **extra, **view_arrays(v), **rest)
     print(f"render_{name}.npz: {W}x{H}, terrain fraction {(g['z24'] != 0xFFFFFF).mean():.3f}")
 
 
@@ -284,7 +302,7 @@ def main():
     # full draws (G1..G5)
     render_fixture("G1_partial", 32, 256, 64, -40, 100)
     render_fixture("G2_full360", 32, 256, 64, -180, 180)
-    render_fixture("G3_cfg1", 600, 2000, 500, -180, 180, keep_depth=False)
+    render_fixture("G3_cfg1", 600, 2000, 500, -180, 180, keep_depth=False, keep_mosaic=False)
     for k, (dlat, dlon) in enumerate([(0.0, 0.0), (0.013, -0.021), (-0.02, 0.017), (0.031, 0.029)]):
         render_fixture(f"G4_move{k}", 64, 512, 128, -180, 180, lat=LAT + dlat, lon=LON + dlon, zfar=8000.0)
     render_fixture("G5_zextents", 64, 512, 128, 20, 200, znear=300.0, zfar=5000.0, znear_color=1000.0, zfar_color=2500.0)

@@ -1,5 +1,5 @@
-import sys
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os, sys
+_T = os.path.dirname(os.path.abspath(__file__)); sys.path.insert(0, os.path.dirname(_T)); sys.path.insert(0, _T)
 import numpy as np
 import hzutil, oracle
 LAT,LON=hzutil.VIEW_LAT,hzutil.VIEW_LON

@@ -25,6 +25,24 @@ def dem_dir(lat_lo, lat_hi, lon_lo, lon_hi, srtm1=False, rough=False):
     return d
 
 
+def load_render_fixture(path):
+    """tests/golden/render_*.npz as a dict.  A fixture whose DEM window is too large to commit along with it
+    (render_G3_cfg1: 1200x1200 samples) holds the SHA-256 of that int16 mosaic and its radius instead; the mosaic is
+    then rebuilt from the synthetic tiles it was cut from (oracle/make_golden.py: render_fixture) and must hash the same"""
+    import hashlib
+    with np.load(path) as z:
+        g = {k: z[k] for k in z.files}
+    if "mosaic" not in g:
+        import oracle
+        R = int(g["mosaic_R"])
+        m = oracle.Dem(VIEW_LAT, VIEW_LON, dem_dir_for(VIEW_LAT, VIEW_LON, R), radius_cells=R).mosaic()
+        if hashlib.sha256(np.ascontiguousarray(m).tobytes()).hexdigest() != str(g["mosaic_sha256"]):
+            raise AssertionError(f"{os.path.basename(path)}: the synthetic DEM generator produced different tiles on this "
+                                 "machine (libm?): the fixture's mosaic cannot be rebuilt")
+        g["mosaic"] = m
+    return g
+
+
 def tiles_for(lat, lon, radius_cells, srtm1=False):
     """integer lat/lon box a window of radius_cells around (lat,lon) can touch"""
     cpd = 3600 if srtm1 else 1200

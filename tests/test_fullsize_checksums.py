@@ -230,7 +230,7 @@ def test_api_full_size_is_the_reference_render(name):
 @pytest.mark.gpu
 def test_api_cfg1_is_the_reference_render():
     """BASELINE.json configs[0] (one tile, 2000x500) through the API against the committed llvmpipe render"""
-    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "render_G3_cfg1.npz"))
+    g = hzutil.load_render_fixture(os.path.join(os.path.dirname(__file__), "golden", "render_G3_cfg1.npz"))
     W, H = int(g["W"]), int(g["H"])
     image, ranges, index, z24, v = _api_render(hzutil.VIEW_LAT, hzutil.VIEW_LON, 600, W, H, -180.0, 180.0,
                                                hzutil.VIEW_LAT, hzutil.VIEW_LON, 100.0, 40000.0)

@@ -20,9 +20,10 @@ def _bench(*args, timeout=600):
     if not hzutil.hip_available():
         pytest.skip("no HIP device")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    # a child process of its own (never an exec from a process that has touched the GPU)
+    # a child process of its own (never an exec from a process that has touched the GPU); --full: the line's checks
+    # (the gathered panorama against the single-GPU render, the other gather mode, one panorama's latency) are --full's
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-host", "--no-extra", *args],
+                        "--full", "--no-cpu-baseline", "--no-host", "--no-extra", *args],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -27,7 +27,7 @@ def _view(g):
 @pytest.mark.parametrize("raster", RASTERS)
 @pytest.mark.parametrize("name", RENDERS)
 def test_golden_scenes_bit_exact_vs_oracle_and_vs_reference(name, raster):
-    g = np.load(os.path.join(GOLD, f"render_{name}.npz"))
+    g = hzutil.load_render_fixture(os.path.join(GOLD, f"render_{name}.npz"))
     W, H, v = int(g["W"]), int(g["H"]), _view(g)
     hip = hzutil.hip_render(g["mosaic"], v, W, H, raster=raster)
     orc = oracle.render(g["mosaic"], v, W, H)

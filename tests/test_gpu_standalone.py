@@ -1,6 +1,7 @@
-"""The reference's own command-line program on the MI355X: standalone.c + annotator.c, compiled in the
-build container where they lie in /root/reference and linked UNCHANGED against include/ + libhorizonator.so
-(tests/caller_stubs/Makefile; stand-ins only for the CLI's own dependencies), run here as a child process.
+"""The reference's own command-line program on the MI355X: standalone.c + annotator.c, compiled by build()
+where the reference's sources are and linked UNCHANGED against include/ + libhorizonator.so
+(oracle/Makefile: oracle/_ref/standalone_ref; tests/caller_stubs: stand-ins only for the CLI's own dependencies),
+run here as a child process.
 Its --image out.png path is horizonator_init / set_zextents / pan_zoom / render_offscreen (reference
 standalone.c:433-460) and then FreeImage, whose stand-in writes the bytes it is handed to the file: they
 must be the bytes this library's Python mirror renders for the same view.  The .pdf path additionally
@@ -15,7 +16,7 @@ import hzutil
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "caller_stubs", "_built", "standalone_ref")
+EXE = os.path.join(ROOT, "oracle", "_ref", "standalone_ref")
 
 
 def _read_raw(path):
@@ -29,10 +30,10 @@ def _read_raw(path):
 def test_the_reference_cli_renders_through_this_library(tmp_path):
     import horizonator_amd
     if not os.path.exists(EXE):
-        # the binary is built where /root/reference is (the build container) and travels with the tree, untracked: on a
+        # the binary is built where the reference's sources are and travels with oracle/_ref, untracked: on a
         # box that got neither, this test cannot run - and says so where a -q run shows it (pytest.ini: -rs)
         why = (f"NOT RUN: {os.path.relpath(EXE, ROOT)} is missing - the reference's standalone.c is linked against this library only "
-               "where /root/reference exists (python -c 'import __graft_entry__ as g; g.build()' in the build container)")
+               "where the reference's sources are (oracle/Makefile, REF)")
         print("\n" + why, flush=True)
         pytest.skip(why)
     # the binary is the one linked against THIS build of the library (it is untracked and travels with the tree)

@@ -6,8 +6,8 @@ O=gpurun_out/final5; mkdir -p $O
 PART=${PART:-abc}
 if [[ $PART == *a* ]]; then
 timeout 1700 python -m pytest tests -x -q -m gpu > $O/pytest_full.txt 2>&1; grep -E "passed|failed|error" $O/pytest_full.txt | tail -2
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench.err; echo "bench rc $?" >> $O/bench.err
-timeout 300 python bench.py --steps 50 --warmup 6 --no-cpu-baseline --no-host --no-scenes > $O/bench_k50.json 2>> $O/bench.err
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_k20.json 2> $O/bench.err; echo "bench rc $?" >> $O/bench.err
+timeout 300 python bench.py --steps 50 --warmup 6 --full --no-cpu-baseline --no-host --no-scenes > $O/bench_k50.json 2>> $O/bench.err
 HZ_HOST_TIMES=1 timeout 400 python tools/host_inclusive.py cfg3 > $O/host_inclusive.txt 2>&1
 timeout 300 python tools/host_inclusive.py cfg3 sectors=1,2,3,4 >> $O/host_inclusive.txt 2>&1
 timeout 300 python tools/host_inclusive.py cfg2 >> $O/host_inclusive.txt 2>&1
@@ -29,8 +29,8 @@ cp gpurun_out/pmc_r5_mix.json $O/ 2>/dev/null
 fi
 if [[ $PART == *c* ]]; then
 timeout 900 python tools/hiz_ab.py cfg3_zoom45 cfg3_zoom45_east cfg3_zoom45_south cfg3_zoom45_summit cfg3_zoom45_valley cfg3_zoom45_rough cfg3_zoom10 --steps 10 --set "HZ_VERTEX_CACHE=0" --set "HZ_VERTEX_CACHE=1" 2>&1 | python tools/hiz_ab_table.py | grep "|\|same_bytes" > $O/zoomed.txt
-timeout 600 python bench.py --gpus 4 --backend gloo --same-gpu --steps 8 --warmup 2 --no-cpu-baseline --no-host --no-extra --loop c 2>>$O/multi.err | grep "^{" > $O/multi_4ranks_one_gpu_c_loop.json
-BENCH_HOST_TIMES=1 timeout 300 python bench.py --gpus 1 --exchange-anyway --steps 20 --warmup 4 --no-cpu-baseline --no-host --no-extra 2>>$O/multi.err | grep "^{" > $O/exchange_anyway.json
+timeout 600 python bench.py --gpus 4 --backend gloo --same-gpu --steps 8 --warmup 2 --full --no-cpu-baseline --no-host --no-extra --loop c 2>>$O/multi.err | grep "^{" > $O/multi_4ranks_one_gpu_c_loop.json
+BENCH_HOST_TIMES=1 timeout 300 python bench.py --gpus 1 --exchange-anyway --steps 20 --warmup 4 --full --no-cpu-baseline --no-host --no-extra 2>>$O/multi.err | grep "^{" > $O/exchange_anyway.json
 python tools/sector_timing.py > $O/sector_timing.txt 2>&1
 bash tools/gpu_scene_kernels.sh cfg3_zoom45_summit > $O/summit_kernels.txt 2>&1
 bash tools/gpu_modes.sh > $O/modes.txt 2>&1

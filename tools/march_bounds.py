@@ -13,7 +13,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import experiments as ex
 
-BENCH = ["bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-host", "--no-scenes", "--zfar", "600000"]
+BENCH = ["bench.py", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-host", "--no-scenes", "--zfar", "600000"]
 
 
 def run(root, env):

@@ -78,6 +78,45 @@ def dem_fixtures():
     print("dem_samples.npz:", len(cases), "cases")
 
 
+def dem_world_fixtures():
+    """reference dem.c away from the N/W quadrant (hzutil.WORLD_CASES: across the equator and the prime meridian, the S/E
+    quadrant, 69.98 N with a tile missing), on tiles that hold voids, negative heights and heights above 16383
+    (hzutil.write_hgt_tiles): window arithmetic, samples over the window's borders and beyond, and the whole
+    mosaic's SHA-256"""
+    import hashlib
+    ref = oracle.load_ref_dem()
+    out = {}
+    for k, (name, c) in enumerate(hzutil.WORLD_CASES.items()):
+        d = hzutil.world_dem_dir(name)
+        ctx = oracle._RefDemCtx()
+        assert ref.horizonator_dem_init(C.byref(ctx), c["lat"], c["lon"], c["R"], -1.0, d.encode(), False), name
+        N = 2 * ctx.radius_cells
+        rng = np.random.default_rng(500 + k)
+        ii = np.concatenate([rng.integers(-2, N + 2, 6000), np.arange(-1, N + 1), np.arange(-1, N + 1)])
+        jj = np.concatenate([rng.integers(-2, N + 2, 6000), np.full(N + 2, 0), np.full(N + 2, N - 1)])
+        for a, other in ((0, jj), (1, ii)):             # the tile seams, both axes
+            seam = ctx.cells_per_deg - ctx.origin_dem_cellij[a]
+            if 0 < seam < N:
+                along = rng.integers(0, N, 150)
+                across = np.concatenate([np.full(50, seam), np.full(50, seam - 1), np.full(50, seam + 1)])
+                ii = np.concatenate([ii, across if a == 0 else along])
+                jj = np.concatenate([jj, along if a == 0 else across])
+        vals = np.array([ref.horizonator_dem_sample(C.byref(ctx), int(i), int(j)) for i, j in zip(ii, jj)], np.int16)
+        m = np.array([[ref.horizonator_dem_sample(C.byref(ctx), i, j) for i in range(N)] for j in range(N)], np.int16)
+        b = [C.c_float() for _ in range(4)]
+        ref.horizonator_dem_bounds_latlon_deg(C.byref(ctx), *[C.byref(x) for x in b])
+        out[f"{name}_window"] = np.array(list(ctx.origin_dem_lon_lat) + list(ctx.origin_dem_cellij) +
+                                         list(ctx.Ndems_ij) + [ctx.radius_cells, ctx.cells_per_deg], np.int32)
+        out[f"{name}_bounds"] = np.array([x.value for x in b], np.float32)
+        out[f"{name}_ij"] = np.stack([ii, jj]).astype(np.int32)
+        out[f"{name}_z"] = vals
+        out[f"{name}_mosaic_sha256"] = np.array(hashlib.sha256(m.tobytes()).hexdigest())
+        out[f"{name}_zero_fraction"] = np.float64((m == 0).mean())
+        ref.horizonator_dem_deinit(C.byref(ctx))
+        print(f"dem world {name}: window {[int(x) for x in out[name + '_window']]}, {100 * (m == 0).mean():.1f}% sea level, max {m.max()}")
+    savez_fixed(os.path.join(OUT, "dem_samples_world.npz"), **out)
+
+
 def vertex_fixture(name, R, W, H, az0, az1, lat=LAT, lon=LON, **kw):
     d = hzutil.dem_dir_for(LAT, LON, R)
     od = oracle.Dem(LAT, LON, d, radius_cells=R)
@@ -98,6 +137,22 @@ def savez_lzma(path, **arrays):
             buf = io.BytesIO()
             np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
             z.writestr(k + ".npy", buf.getvalue())
+
+
+def savez_fixed(path, **arrays):
+    """savez_lzma with a fixed time stamp and mode on every member: the same arrays give the same file, byte for byte.
+    A function of its own because the fixtures written with savez_lzma carry the time of their making: writing those
+    again would change committed files that nothing else touches"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w") as z:
+        for k, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_LZMA
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
 
 
 def render_fixture(name, R, W, H, az0, az1, lat=LAT, lon=LON, keep_depth=True, rough=False, keep_mosaic=True, **kw):
@@ -253,6 +308,34 @@ def random_checksum_fixtures():
     json.dump(out, open(os.path.join(OUT, "random_checksums.json"), "w"), indent=1)
 
 
+ZOO_RENDERS = {"Z1_cliff_z005": "cliff-z005", "Z2_checker_near360": "checker-near360", "Z3_border_minus1_vertex360": "border_minus1-vertex360"}
+
+
+def zoo_checksum_fixtures():
+    """the terrain zoo (hzutil.zoo_cases: hand-made ground crossed with views): SHA-256 of the reference's draw
+    of every case, next to the mosaic's hash and the uniform values; three small cases also as images"""
+    import hashlib
+    import json
+    out = {}
+    for c in hzutil.zoo_cases():
+        m = hzutil.zoo_mosaic(c["family"], c["N"])
+        v = oracle.make_view(**c["view"])
+        g = glsl_run.render(m, v, c["W"], c["H"])
+        out[c["name"]] = {"family": c["family"], "N": c["N"], "W": c["W"], "H": c["H"], "degenerate": c["degenerate"],
+                          "view": hzutil.zoo_view_json({k: float(np.float32(x)) for k, x in v.as_dict().items()}),
+                          "mosaic_sha256": hashlib.sha256(m.tobytes()).hexdigest(),
+                          "bgr_sha256": hashlib.sha256(g["bgr"].tobytes()).hexdigest(),
+                          "z24_sha256": hashlib.sha256(g["z24"].tobytes()).hexdigest(),
+                          "terrain_fraction": float((g["z24"] != 0xFFFFFF).mean())}
+        print(f"zoo {c['name']}: N={c['N']} {c['W']}x{c['H']} terrain {out[c['name']]['terrain_fraction']:.3f}")
+        for fixture, name in ZOO_RENDERS.items():
+            if name == c["name"]:
+                savez_fixed(os.path.join(OUT, f"render_{fixture}.npz"), mosaic=m, W=np.int32(c["W"]), H=np.int32(c["H"]),
+                           bgr=g["bgr"], z24=g["z24"], depth=g["depth"], **view_arrays(v))
+    with open(os.path.join(OUT, "zoo_checksums.json"), "w") as f:
+        json.dump(out, f, indent=1, allow_nan=False)     # strict JSON: an infinite extent is the string "inf"
+
+
 def raster_probe_fixture():
     """llvmpipe's fill rule and depth rounding on hand-made triangles (our own
     pass-through shaders; no reference code involved)"""
@@ -293,7 +376,14 @@ def main():
     if sys.argv[1:] == ["texture"]:             # only the texture path's fixtures
         texture_fixtures()
         return
+    if sys.argv[1:] == ["zoo"]:                 # only the terrain zoo's fixtures
+        zoo_checksum_fixtures()
+        return
+    if sys.argv[1:] == ["world"]:               # only tests/golden/dem_samples_world.npz
+        dem_world_fixtures()
+        return
     dem_fixtures()
+    dem_world_fixtures()
     raster_probe_fixture()
     # vertex stage (pins reference vertex.glsl:111-162 bit for bit)
     vertex_fixture("full360", 64, 256, 64, -180, 180)
@@ -313,6 +403,7 @@ def main():
     batch_checksum_fixtures()
     random_checksum_fixtures()
     texture_fixtures()
+    zoo_checksum_fixtures()
 
 
 if __name__ == "__main__":

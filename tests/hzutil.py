@@ -206,3 +206,200 @@ def assert_same_render(a, b, what=""):
                 bad = np.argwhere(a[k] != b[k])
                 raise AssertionError(f"{what}: {k} differs at {len(bad)} places, first {bad[0]}: "
                                      f"{a[k][tuple(bad[0])]} vs {b[k][tuple(bad[0])]}")
+
+
+# ---- the terrain zoo: hand-made ground, integer arithmetic only --------------
+
+def _zoo_hash(i, j, seed):
+    """64-bit integer hash of a sample position (the hash_texture mix): uint64, same bytes on every machine"""
+    i = np.asarray(i).astype(np.uint64); j = np.asarray(j).astype(np.uint64)
+    h = (i * np.uint64(73856093)) ^ (j * np.uint64(19349663)) ^ np.uint64(83492791 + seed * 2654435761)
+    h = (h ^ (h >> np.uint64(13))) * np.uint64(0x9E3779B97F4A7C15)
+    return (h ^ (h >> np.uint64(29))) >> np.uint64(20)
+
+
+def _isqrt(a):
+    """floor(sqrt(a)) of a non-negative int64 array, corrected with integer compares"""
+    r = np.sqrt(a.astype(np.float64)).astype(np.int64)
+    r -= (r * r > a)
+    r += ((r + 1) * (r + 1) <= a)
+    return r
+
+
+ZOO_FAMILIES = ("flat0", "plateau", "checker", "spikes", "cliff", "coast", "max16", "border_minus1", "bowl", "stairs")
+
+
+def zoo_mosaic(name, N):
+    """hand-made DEM windows for tests/test_gpu_terrain_zoo.py: int16[N,N], row j = north index, column i = east index.
+    No libm, no RNG: fixtures store the name and N, not the samples."""
+    j, i = np.mgrid[0:N, 0:N].astype(np.int64)
+    if name == "flat0":                 # sea level everywhere: what the DEM reader gives for voids and missing tiles
+        m = np.zeros((N, N), np.int64)
+    elif name == "plateau":
+        m = np.full((N, N), 1234, np.int64)
+    elif name == "checker":             # every triangle tall and thin
+        m = np.where((i + j) & 1, 8000, 0)
+    elif name == "spikes":              # isolated one-sample summits
+        m = np.where(_zoo_hash(i, j, 1) % np.uint64(97) == 0, 6000, 200)
+    elif name == "cliff":               # one wall along a meridian three cells east of the centre
+        m = np.where(i < N // 2 + 3, 0, 3000)
+    elif name == "coast":               # half sea level, half blocky land
+        m = np.maximum(0, (_zoo_hash(i // 8, j // 8, 2) % np.uint64(900)).astype(np.int64) - 450)
+    elif name == "max16":               # top bits of the int16
+        m = np.where(_zoo_hash(i, j, 3) & np.uint64(1), 32767, 32000)
+    elif name == "border_minus1":       # the -1 that sampling outside the window returns, next to positive heights
+        m = np.full((N, N), 500, np.int64)
+        m[:2, :] = -1; m[-1, :] = -1; m[:, 0] = -1; m[:, -2:] = -1
+    elif name == "bowl":                # viewer at the bottom: everything above the horizon, nothing hidden
+        c = N // 2
+        m = np.minimum(8000, 60 * _isqrt((i - c) ** 2 + (j - c) ** 2))
+    elif name == "stairs":              # long exactly collinear edges on a slope
+        m = 100 * (j // 16)
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(m.astype(np.int16))
+
+
+# cos(latitude) as float32 constants, so that no case depends on a libm: latitude -> cos_viewer_lat
+_ZOO_COS = {0.0: 1.0, 34.4: 0.8251135, -43.6: 0.7241719, 69.6: 0.3485720, 80.0: 0.1736482}
+
+# view recipes: N, W, H, viewer position ("off" = a fraction of a cell off the centre, "vertex" = exactly on the centre
+# sample, "corner" = a few cells from the window's south-west corner), viewer height (a number, or "above" = 10 m above the
+# highest of the four samples around the viewer), latitude, cells per degree, azimuth extents, depth extents, colour extents
+_ZOO_VIEWS = {
+    "near360":   dict(N=64,  W=640,  H=160, pos="off",    vz="above", lat=34.4,  cpd=1200, az=(-180.0, 180.0), z=(100.0, 40000.0)),
+    "high_wrap": dict(N=200, W=640,  H=160, pos="off",    vz=2500.0,  lat=-43.6, cpd=1200, az=(170.0, 530.0),  z=(10.0, 300000.0)),
+    "arctic90":  dict(N=128, W=801,  H=203, pos="off",    vz="above", lat=69.6,  cpd=3600, az=(-45.0, 45.0),   z=(1.0, 2000.0)),
+    "sky":       dict(N=400, W=1024, H=256, pos="off",    vz=9000.0,  lat=34.4,  cpd=1200, az=(-180.0, 180.0), z=(100.0, 100000.0),
+                      zc=(2000.0, 30000.0)),
+    "zoom12":    dict(N=96,  W=333,  H=111, pos="vertex", vz="above", lat=80.0,  cpd=1200, az=(354.0, 366.0),   z=(10.0, 20000.0)),
+    "corner90":  dict(N=400, W=1024, H=256, pos="corner", vz=2500.0,  lat=0.0,   cpd=1200, az=(0.0, 90.0),     z=(100.0, 300000.0)),
+    "z005":      dict(N=64,  W=512,  H=128, pos="off",    vz=0.005,   lat=34.4,  cpd=1200, az=(-180.0, 180.0), z=(1.0, 9000.0)),
+    # depth steps of 30 m: overlapping triangles tie in z24 and the lower triangle id must win
+    "coarse_z":  dict(N=64,  W=640,  H=160, pos="off",    vz="above", lat=34.4,  cpd=1200, az=(-180.0, 180.0), z=(100.0, 5e8),
+                      zc=(100.0, 40000.0)),
+    # "no far limit" as a caller may write it: every quotient by the colour span is exactly 0
+    "inf_color": dict(N=64,  W=640,  H=160, pos="off",    vz="above", lat=34.4,  cpd=1200, az=(-180.0, 180.0), z=(100.0, 40000.0),
+                      zc=(100.0, float("inf"))),
+    # ... and no far clip: every vertex has depth exactly -1, all of the terrain ties at z24 = 0 and the lowest triangle id wins
+    # everywhere; the abridged quotient by the depth span would be NaN (hzf_draw_ok refuses the draw).  The reference's own
+    # range formula gives 0 * inf = NaN on terrain here
+    "inf_far":   dict(N=64,  W=640,  H=160, pos="off",    vz="above", lat=34.4,  cpd=1200, az=(-180.0, 180.0), z=(100.0, float("inf")),
+                      zc=(100.0, 40000.0)),
+    "vertex360": dict(N=64,  W=512,  H=128, pos="vertex", vz="above", lat=-43.6, cpd=3600, az=(-180.0, 180.0), z=(10.0, 8000.0),
+                      zc=(50.0, 1500.0)),
+}
+
+# family -> (recipe, overrides) ...: the cross of ground and view, written out so that a reader sees every case
+_ZOO_PLAN = {
+    "flat0":         [("near360", {}), ("high_wrap", {}), ("sky", {}), ("zoom12", {}), ("corner90", {}),
+                      ("z005", dict(degenerate=True))],                                        # 5 mm above sea level: a line
+    "plateau":       [("near360", dict(vz=1300.0)), ("high_wrap", {}), ("arctic90", {}), ("sky", {}),
+                      ("vertex360", dict(vz=1234.0, degenerate=True))],                       # edge-on: viewer AT the plateau's height
+    "checker":       [("near360", {}), ("high_wrap", dict(vz=8500.0)), ("arctic90", {}), ("sky", {}), ("vertex360", dict(vz=4000.0)),
+                      ("coarse_z", {}), ("zoom12", dict(vz=4000.0, degenerate=True))],                           # from inside the checkerboard: all terrain
+    "spikes":        [("near360", {}), ("high_wrap", {}), ("arctic90", {}), ("corner90", {}), ("vertex360", dict(vz=100.0)), ("zoom12", {}),
+                      ("coarse_z", {}), ("inf_color", {}), ("inf_far", {})],
+    "cliff":         [("near360", {}), ("high_wrap", {}), ("arctic90", {}), ("z005", {}), ("sky", {}), ("inf_color", {})],
+    "coast":         [("near360", {}), ("high_wrap", {}), ("arctic90", {}), ("sky", {}), ("corner90", {}), ("zoom12", {}), ("coarse_z", {}),
+                      ("inf_far", {})],
+    "max16":         [("near360", {}), ("arctic90", {}), ("vertex360", {}), ("sky", dict(vz=34000.0))],
+    "border_minus1": [("near360", {}), ("high_wrap", {}), ("corner90", dict(vz=700.0)), ("sky", {}), ("vertex360", {})],
+    "bowl":          [("near360", {}), ("high_wrap", {}), ("z005", {}), ("arctic90", {}), ("vertex360", {})],
+    "stairs":        [("near360", {}), ("high_wrap", {}), ("corner90", {}), ("vertex360", dict(vz=150.0)), ("zoom12", {})],
+}
+
+
+def zoo_view_json(view):
+    """a case's uniform values as strict JSON takes them: finite floats as they are, an infinite extent as the string "inf"""
+    return {k: (x if np.isfinite(x) else {float("inf"): "inf", float("-inf"): "-inf"}[x]) for k, x in view.items()}
+
+
+def zoo_cases():
+    """the terrain zoo's case list, deterministic: dicts with name, family, N, W, H, view (the twelve uniform values as
+    float32-representable floats), c0, c1 (a sector on every other case) and degenerate (the reference draws nothing or
+    everything: wanted, but exempt from the terrain-fraction condition)"""
+    f32 = np.float32
+    cases = []
+    for family in ZOO_FAMILIES:
+        for recipe, over in _ZOO_PLAN[family]:
+            r = dict(_ZOO_VIEWS[recipe]); r.update(over)
+            N, W, H = r["N"], r["W"], r["H"]
+            k = len(cases)
+            if r["pos"] == "off":
+                ci, cj = f32(N // 2) + f32(0.37), f32(N // 2) - f32(0.29)
+            elif r["pos"] == "vertex":
+                ci, cj = f32(N // 2), f32(N // 2)
+            else:
+                ci, cj = f32(5.3), f32(7.6)
+            vz = r["vz"]
+            if vz == "above":
+                m = zoo_mosaic(family, N)
+                i0, j0 = int(np.floor(ci)), int(np.floor(cj))
+                vz = float(m[j0:j0 + 2, i0:i0 + 2].max()) + 10.0
+            zc = r.get("zc", r["z"])
+            view = dict(viewer_cell_i=ci, viewer_cell_j=cj, viewer_z=f32(vz), cos_viewer_lat=f32(_ZOO_COS[r["lat"]]),
+                        deg_per_cell=f32(1.0) / f32(r["cpd"]), az_deg0=f32(r["az"][0]), az_deg1=f32(r["az"][1]),
+                        aspect=f32(W) / f32(H), znear=f32(r["z"][0]), zfar=f32(r["z"][1]),
+                        znear_color=f32(zc[0]), zfar_color=f32(zc[1]))
+            c0, c1 = (W // 5 + k, W // 5 + k + W // 3) if k % 2 else (0, W)
+            cases.append(dict(name=f"{family}-{recipe}", family=family, recipe=recipe, lat=r["lat"], N=N, W=W, H=H,
+                              view={n: float(x) for n, x in view.items()}, c0=c0, c1=c1,
+                              degenerate=bool(r.get("degenerate", False))))
+    assert len({c["name"] for c in cases}) == len(cases)
+    return cases
+
+
+# ---- .hgt tiles anywhere on Earth, with what real SRTM holds and tools/demgen.c does not write ----------------
+
+def hgt_tile_name(lat, lon):
+    """file name of the tile whose south-west corner is (lat, lon), integers: N/S + 2 digits, E/W + 3 digits"""
+    return "%s%02d%s%03d.hgt" % ("S" if lat < 0 else "N", abs(lat), "W" if lon < 0 else "E", abs(lon))
+
+
+def hgt_tile_values(lat, lon, cpd=1200):
+    """int16[cpd+1,cpd+1], row 0 = northern edge: integer-hash terrain keyed on the absolute sample position (tiles
+    agree along shared edges), blocky hills with sea-level flats, and sprinkled over them negative heights,
+    -32768 voids and heights above 16383"""
+    row, col = np.mgrid[0:cpd + 1, 0:cpd + 1].astype(np.int64)
+    gi = (lon + 400) * cpd + col                 # absolute east index, offset to stay positive
+    gj = (lat + 400) * cpd + (cpd - row)         # absolute north index
+    z = np.maximum(0, (_zoo_hash(gi // 12, gj // 12, 11) % np.uint64(2400)).astype(np.int64) - 800)
+    z = np.where(z > 0, z + (_zoo_hash(gi, gj, 12) % np.uint64(40)).astype(np.int64), 0)
+    h = _zoo_hash(gi, gj, 13)
+    z = np.where(h % np.uint64(31) == 0, -32768, z)
+    z = np.where(h % np.uint64(29) == 1, -1 - (h % np.uint64(400)).astype(np.int64), z)
+    z = np.where(h % np.uint64(37) == 2, 16384 + (h % np.uint64(16000)).astype(np.int64), z)
+    return z.astype(np.int16)
+
+
+def write_hgt_tiles(directory, lat_lo, lat_hi, lon_lo, lon_hi, cpd=1200, missing=()):
+    """big-endian int16 tiles covering the integer box, except those named in `missing`"""
+    os.makedirs(directory, exist_ok=True)
+    for lat in range(lat_lo, lat_hi + 1):
+        for lon in range(lon_lo, lon_hi + 1):
+            name = hgt_tile_name(lat, lon)
+            path = os.path.join(directory, name)
+            if name[:-4] in missing or os.path.exists(path) and os.path.getsize(path) == 2 * (cpd + 1) ** 2:
+                continue
+            tmp = path + ".%d.tmp" % os.getpid()
+            hgt_tile_values(lat, lon, cpd).astype(">i2").tofile(tmp)
+            os.replace(tmp, path)
+    return directory
+
+
+# places away from the N/W quadrant: name -> viewpoint, window radius, the tiles the window touches, the tile left out,
+# a second viewpoint inside the window
+WORLD_CASES = {
+    "equator_greenwich": dict(lat=0.0137, lon=-0.0121, R=100, tiles=("S01W001", "S01E000", "N00W001", "N00E000"), missing=(),
+                              moved=(-0.021, 0.033)),
+    "south_east":        dict(lat=-43.6, lon=170.1, R=150, tiles=("S44E169", "S44E170"), missing=(), moved=(-43.63, 170.02)),
+    "arctic_gap":        dict(lat=69.98, lon=20.03, R=120, tiles=("N69E019", "N69E020", "N70E019", "N70E020"),
+                              missing=("N70E020",), moved=(70.01, 19.97)),
+}
+
+
+def world_dem_dir(name):
+    """directory with the tiles of WORLD_CASES[name] (generated on first use, cached)"""
+    c = WORLD_CASES[name]
+    return write_hgt_tiles(os.path.join(_DEM_ROOT, "world_" + name), *tiles_for(c["lat"], c["lon"], c["R"]), missing=c["missing"])

@@ -145,3 +145,75 @@ def test_public_api_refuses_more_than_4x4_tiles():
     ctx = _lib.DemContext()
     d = hzutil.dem_dir_for(hzutil.VIEW_LAT, hzutil.VIEW_LON, 2100).encode()
     assert not lib.horizonator_dem_init(C.byref(ctx), hzutil.VIEW_LAT, hzutil.VIEW_LON, 2100, -1.0, d, False)
+
+
+# ---- elsewhere on Earth (tests/golden/dem_samples_world.npz: the reference's dem.c on hzutil.write_hgt_tiles' tiles) ----
+
+WORLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "dem_samples_world.npz"))
+
+
+def test_hgt_tile_names_in_all_four_quadrants():
+    assert [hzutil.hgt_tile_name(*t) for t in ((0, 0), (-1, -1), (-44, 170), (70, 20), (34, -118), (-1, 0), (0, -1))] == \
+        ["N00E000.hgt", "S01W001.hgt", "S44E170.hgt", "N70E020.hgt", "N34W118.hgt", "S01E000.hgt", "N00W001.hgt"]
+    for name, c in hzutil.WORLD_CASES.items():
+        d = hzutil.world_dem_dir(name)
+        assert sorted(os.listdir(d)) == sorted(t + ".hgt" for t in c["tiles"] if t not in c["missing"]), name
+
+
+def test_world_tiles_hold_voids_negatives_and_high_samples_and_agree_on_shared_edges():
+    """what the writer is for: raw tile values the synthetic generator of tools/ never writes"""
+    a, b, c = hzutil.hgt_tile_values(-1, -1), hzutil.hgt_tile_values(-1, 0), hzutil.hgt_tile_values(0, -1)
+    assert (a == -32768).any() and ((a < 0) & (a > -32768)).any() and (a > 16383).any() and (a == 0).mean() > 0.2
+    assert np.array_equal(a[:, -1], b[:, 0])          # eastern edge = the next tile's western edge
+    assert np.array_equal(a[0, :], c[-1, :])          # northern edge = the next tile's southern edge
+    raw = np.fromfile(os.path.join(hzutil.world_dem_dir("equator_greenwich"), "S01W001.hgt"), ">i2").reshape(1201, 1201)
+    assert np.array_equal(raw, a)
+
+
+@pytest.mark.parametrize("name", sorted(hzutil.WORLD_CASES))
+def test_oracle_dem_matches_reference_dem_c_elsewhere_on_earth(name):
+    c = hzutil.WORLD_CASES[name]
+    od = oracle.Dem(c["lat"], c["lon"], hzutil.world_dem_dir(name), radius_cells=c["R"])
+    got = list(od.d.origin_tile) + list(od.d.origin_cell) + list(od.d.ntiles) + [od.d.radius_cells, od.d.cells_per_deg]
+    assert got == list(WORLD[f"{name}_window"])
+    ii, jj = WORLD[f"{name}_ij"]
+    z = np.array([od.sample(i, j) for i, j in zip(ii, jj)], np.int16)
+    assert np.array_equal(z, WORLD[f"{name}_z"])
+    m = od.mosaic()
+    import hashlib
+    assert hashlib.sha256(m.tobytes()).hexdigest() == str(WORLD[f"{name}_mosaic_sha256"])
+    # voids and negatives read as sea level, high samples survive
+    assert m.min() == 0 and m.max() > 16383 and (m == 0).mean() == float(WORLD[f"{name}_zero_fraction"])
+
+
+@pytest.mark.parametrize("name", sorted(hzutil.WORLD_CASES))
+def test_product_dem_matches_reference_dem_c_elsewhere_on_earth(name):
+    import hashlib
+    c = hzutil.WORLD_CASES[name]
+    d = hzutil.world_dem_dir(name)
+    lib = _lib.load()
+    ctx = _lib.DemContext()
+    assert lib.horizonator_dem_init(C.byref(ctx), c["lat"], c["lon"], c["R"], -1.0, d.encode(), False)
+    got = list(ctx.origin_dem_lon_lat) + list(ctx.origin_dem_cellij) + list(ctx.Ndems_ij) + [ctx.radius_cells, ctx.cells_per_deg]
+    assert got == list(WORLD[f"{name}_window"])
+    ii, jj = WORLD[f"{name}_ij"]
+    z = np.array([lib.horizonator_dem_sample(C.byref(ctx), int(i), int(j)) for i, j in zip(ii, jj)], np.int16)
+    assert np.array_equal(z, WORLD[f"{name}_z"])
+    b = [C.c_float() for _ in range(4)]
+    lib.horizonator_dem_bounds_latlon_deg(C.byref(ctx), *[C.byref(x) for x in b])
+    assert np.array_equal(np.array([x.value for x in b], np.float32), WORLD[f"{name}_bounds"])
+    lib.horizonator_dem_deinit(C.byref(ctx))
+    # and the mosaic the library uploads (hz_dem.c's tile table, no GPU involved)
+    m = _product_mosaic(c["lat"], c["lon"], c["R"], d)
+    assert hashlib.sha256(m.tobytes()).hexdigest() == str(WORLD[f"{name}_mosaic_sha256"])
+
+
+def test_missing_tile_inside_the_window_reads_sea_level():
+    """arctic_gap leaves N70E020 out: the window's north-east part is exactly 0, the rest is not"""
+    c = hzutil.WORLD_CASES["arctic_gap"]
+    od = oracle.Dem(c["lat"], c["lon"], hzutil.world_dem_dir("arctic_gap"), radius_cells=c["R"])
+    m = od.mosaic()
+    si, sj = 1200 - od.d.origin_cell[0], 1200 - od.d.origin_cell[1]      # first column / row served by the tiles east / north
+    assert 0 < si < m.shape[1] - 1 and 0 < sj < m.shape[0] - 1
+    assert not m[sj + 1:, si + 1:].any()
+    assert m[:sj + 1, :].any() and m[sj + 1:, :si + 1].any()

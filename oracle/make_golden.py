@@ -336,6 +336,35 @@ def zoo_checksum_fixtures():
         json.dump(out, f, indent=1, allow_nan=False)     # strict JSON: an infinite extent is the string "inf"
 
 
+def zoo_tex_checksum_fixtures():
+    """the textured zoo (hzutil.zoo_tex_cases: zoo cases under texture placements that wrap, minify, magnify, flip and
+    straddle the seam): SHA-256 of the reference's textured draw of every entry.  An entry on which the oracle's textured
+    draw differs from llvmpipe's is not written: the GPU tests take index and ranges from the oracle on its strength"""
+    import hashlib
+    import json
+    zoo = {c["name"]: c for c in hzutil.zoo_cases()}
+    out = {}
+    for e in hzutil.zoo_tex_cases():
+        c = zoo[e["name"]]
+        m = hzutil.zoo_mosaic(c["family"], c["N"])
+        v = oracle.make_view(**c["view"])
+        t, texels = hzutil.zoo_tex_inputs(e, c)
+        t = hzutil.orc_tex(t)
+        g = glsl_run.render_textured(m, v, c["W"], c["H"], t.as_glsl_job(), texels)
+        o = oracle.render(m, v, c["W"], c["H"], tex=t, texels=texels, want=("bgr", "z24"))
+        if not (np.array_equal(o["bgr"], g["bgr"]) and np.array_equal(o["z24"], g["z24"])):
+            sys.exit(f"zootex {e['id']}: the oracle's textured draw differs from llvmpipe's on "
+                     f"{int((o['bgr'] != g['bgr']).any(-1).sum())} pixels (depth: {int((o['z24'] != g['z24']).sum())}); nothing written")
+        out[e["id"]] = {"name": e["name"], "placement": e["placement"], "ntiles_x": e["ntiles"][0], "ntiles_y": e["ntiles"][1],
+                        "tex_seed": e["seed"], "tex_blocky": e["blocky"],
+                        "bgr_sha256": hashlib.sha256(g["bgr"].tobytes()).hexdigest(),
+                        "z24_sha256": hashlib.sha256(g["z24"].tobytes()).hexdigest(),
+                        "terrain_fraction": float((g["z24"] != 0xFFFFFF).mean())}
+        print(f"zootex {e['id']}: tiles {e['ntiles']} terrain {out[e['id']]['terrain_fraction']:.3f}", flush=True)
+    with open(os.path.join(OUT, "zoo_tex_checksums.json"), "w") as f:
+        json.dump(out, f, indent=1, allow_nan=False)
+
+
 def raster_probe_fixture():
     """llvmpipe's fill rule and depth rounding on hand-made triangles (our own
     pass-through shaders; no reference code involved)"""
@@ -382,6 +411,9 @@ def main():
     if sys.argv[1:] == ["world"]:               # only tests/golden/dem_samples_world.npz
         dem_world_fixtures()
         return
+    if sys.argv[1:] == ["zootex"]:              # only tests/golden/zoo_tex_checksums.json
+        zoo_tex_checksum_fixtures()
+        return
     dem_fixtures()
     dem_world_fixtures()
     raster_probe_fixture()
@@ -404,6 +436,7 @@ def main():
     random_checksum_fixtures()
     texture_fixtures()
     zoo_checksum_fixtures()
+    zoo_tex_checksum_fixtures()
 
 
 if __name__ == "__main__":

@@ -109,6 +109,39 @@ def hash_texture(th, tw, seed=0, blocky=1):
     return out
 
 
+def write_map_tiles(root, name, lowest_x, lowest_y, nx, ny, seed):
+    """zoom-12 map tiles as PNG files in the layout the reference reads
+    (dir_tiles/tiles_name/12/X/Y.png), in the PNG flavours tile servers emit; returns the
+    mosaic as the reference builds it: uint8[ny*256, nx*256, 3] B,G,R, southern row first"""
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    mosaic = np.zeros((ny * 256, nx * 256, 3), np.uint8)
+    highest_y = lowest_y + ny - 1
+    k = 0
+    for ty in range(lowest_y, lowest_y + ny):
+        for tx in range(lowest_x, lowest_x + nx):
+            yy, xx = np.mgrid[0:256, 0:256]
+            rgb = np.stack([(xx * 3 + tx * 40) % 256, (yy * 5 + ty * 17) % 256, (xx + yy + 31 * k) % 256], -1).astype(np.uint8)
+            rgb = (rgb.astype(int) + rng.integers(-20, 21, rgb.shape)).clip(0, 255).astype(np.uint8)
+            img = Image.fromarray(rgb, "RGB")
+            flavour = k % 4
+            if flavour == 1:            # palettised, as OSM's own tiles are (reference :339-352)
+                img = img.quantize(colors=200)
+                rgb = np.asarray(img.convert("RGB"))
+            elif flavour == 2:          # with an alpha channel, which is dropped
+                img = img.convert("RGBA")
+            elif flavour == 3:          # grey
+                img = img.convert("L")
+                rgb = np.repeat(np.asarray(img)[..., None], 3, -1)
+            d = root / name / "12" / str(tx)
+            d.mkdir(parents=True, exist_ok=True)
+            img.save(d / f"{ty}.png")
+            x0, y0 = (tx - lowest_x) * 256, (highest_y - ty) * 256
+            mosaic[y0:y0 + 256, x0:x0 + 256] = rgb[::-1, :, ::-1]      # bottom-up rows, B,G,R
+            k += 1
+    return mosaic
+
+
 # ---- driving the HIP path through its C-ABI (include/hz_hip.h) ---------------
 
 def hip_available():
@@ -158,8 +191,21 @@ class HipDev:
         assert texels.shape == (tp.tex_h, tp.tex_w, 3)
         assert self.lib.hz_hip_set_texture(self.dev, C.byref(tp), texels.ctypes.data) == 0, self.lib.hz_hip_last_error()
 
-    def render(self, view, col0=0, col1=None, tanel=None):
-        """`view` is anything with the hz_view_t field names as attributes (e.g. oracle.OrcView)"""
+    def texture_off(self):
+        assert self.lib.hz_hip_set_texture(self.dev, None, None) == 0
+
+    def set_texparams(self, tex):
+        """the parameters alone, for a resident texture of the same size: the C-ABI's return code (0, or -1 with
+        hz_hip_last_error() set)"""
+        import ctypes as C
+        tp = hzlib.TexParams()
+        for name, _ in hzlib.TexParams._fields_:
+            setattr(tp, name, getattr(tex, name))
+        return self.lib.hz_hip_set_texture(self.dev, C.byref(tp), None)
+
+    def render(self, view, col0=0, col1=None, tanel=None, want=("bgr", "ranges", "index", "z24")):
+        """`view` is anything with the hz_view_t field names as attributes (e.g. oracle.OrcView);
+        `want`: the outputs asked for (NULL goes in for the others), returned as a dict of those"""
         import ctypes as C
         lib, W, H = self.lib, self.W, self.H
         if col1 is None:
@@ -174,18 +220,21 @@ class HipDev:
             import oracle
             tanel = oracle.tanel(W, H, v.az_deg0, v.az_deg1)
         tanel = np.ascontiguousarray(tanel, np.float32)
+        assert want and set(want) <= {"bgr", "ranges", "index", "z24"}
         out = {"bgr": np.empty((H, SW, 3), np.uint8), "ranges": np.empty((H, SW), np.float32),
                "index": np.empty((H, SW), np.int32), "z24": np.empty((H, SW), np.uint32)}
+        out = {k: a for k, a in out.items() if k in want}
+
+        def ptr(k):
+            return out[k].ctypes.data if k in out else None
         # draw + delivery into host memory as one call (hz_hostpath.cpp: in azimuth sectors where the image is large or the
         # context's host_sectors option says so); every other call the two-step form, hz_hip_draw then hz_hip_resolve_to_host
         self.calls = getattr(self, "calls", 0) + 1
         if self.calls % 2:
-            rc = lib.hz_hip_render_to_host(self.dev, C.byref(v), tanel.ctypes.data, out["bgr"].ctypes.data,
-                                           out["ranges"].ctypes.data, out["index"].ctypes.data, out["z24"].ctypes.data)
+            rc = lib.hz_hip_render_to_host(self.dev, C.byref(v), tanel.ctypes.data, ptr("bgr"), ptr("ranges"), ptr("index"), ptr("z24"))
         else:
             assert lib.hz_hip_draw(self.dev, C.byref(v)) == 0, lib.hz_hip_last_error()
-            rc = lib.hz_hip_resolve_to_host(self.dev, C.byref(v), tanel.ctypes.data, out["bgr"].ctypes.data,
-                                            out["ranges"].ctypes.data, out["index"].ctypes.data, out["z24"].ctypes.data)
+            rc = lib.hz_hip_resolve_to_host(self.dev, C.byref(v), tanel.ctypes.data, ptr("bgr"), ptr("ranges"), ptr("index"), ptr("z24"))
         assert rc == 0, lib.hz_hip_last_error()
         return out
 
@@ -348,6 +397,99 @@ def zoo_cases():
                               degenerate=bool(r.get("degenerate", False))))
     assert len({c["name"] for c in cases}) == len(cases)
     return cases
+
+
+# ---- texture placements for the zoo: where the DEM window lies on the mosaic of map tiles -----------------
+
+# placement -> s at the window's west and east edge, t over one window height of latitude, and the curvature
+# dlat2 as a multiple of dlat1/span.  `inside` is what every earlier textured test had; the others put coordinates
+# beyond [0,1] (GL_REPEAT), many texels per pixel, a few texels over the whole window, decreasing s, and the wrap
+# seam itself under the viewer
+ZOO_TEX_PLACEMENTS = {
+    "inside":    ((0.05, 0.95), (0.1, 0.9), 0.0),
+    "wrap":      ((-0.3, 1.4), (-0.2, 1.1), 0.2),
+    "far_out":   ((37.2, 38.9), (-12.6, -11.3), 0.2),
+    "minified":  ((0.0, 40.0), (0.0, 25.0), -0.3),
+    "magnified": ((0.5, 0.5 + 3.0 / 768.0), (0.25, 0.25 + 2.0 / 512.0), 0.0),
+    "flipped":   ((1.2, -0.1), (0.9, 0.1), 0.5),
+    "seam":      ((0.999, 1.001), (-0.001, 0.001), 0.0),
+}
+ZOO_TEX_TILES = ((3, 2), (2, 3), (1, 1), (5, 1), (1, 4))        # 768, 512, 256, 1280, 1024 texels: power of two and not
+ZOO_TEX_BLOCKY = (1, 8, 4)
+ZOO_TEX_FULL_CROSS = ("checker-zoom12", "cliff-z005", "coast-arctic90")
+
+
+def zoo_tex(case, placement, ntiles):
+    """texture parameters (hzlib.TexParams: the hz_texparams_t / oracle.OrcTex field names) that lay zoo case `case`'s
+    DEM window on a mosaic of ntiles = (x, y) map tiles as ZOO_TEX_PLACEMENTS[placement] says.  float32 multiplies,
+    divisions and additions only, so that fixtures store names and not numbers"""
+    f32 = np.float32
+    (s_lo, s_hi), (t_lo, t_hi), curve = ZOO_TEX_PLACEMENTS[placement]
+    ntx, nty = ntiles
+    span = f32(case["N"]) * f32(case["view"]["deg_per_cell"]) * f32(0.017453292)         # the window's extent in radians
+    t = hzlib.TexParams()
+    t.viewer_lat_rad = f32(0.3) * span
+    t.origin_cell_lon_deg = t.origin_cell_lat_deg = 0.0
+    t.ntiles_x, t.ntiles_y, t.lowest_x, t.lowest_y = ntx, nty, 700, 1600
+    t.tex_w, t.tex_h = 256 * ntx, 256 * nty
+    t.lon0 = f32(700) + f32(s_lo) * f32(ntx)
+    t.lon1 = (f32(s_hi) - f32(s_lo)) * f32(ntx) / span
+    t.dlat0 = f32(1600) + f32(nty) * (f32(1) - f32(t_lo))
+    dlat1 = -(f32(t_hi) - f32(t_lo)) * f32(nty) / span
+    t.dlat1 = dlat1
+    t.dlat2 = f32(curve) * (dlat1 / span)
+    return t
+
+
+def orc_tex(t):
+    """oracle.OrcTex with the values of anything that has its field names"""
+    import oracle
+    o = oracle.OrcTex()
+    for name, _ in hzlib.TexParams._fields_:
+        setattr(o, name, getattr(t, name))
+    return o
+
+
+def zoo_tex_cases():
+    """the textured zoo's list, deterministic: every zoo case under one placement in rotation, the three of
+    ZOO_TEX_FULL_CROSS under all seven; tile counts, texture seed and blockiness rotate with the entry's number.
+    dicts with id, name (the zoo case's), placement, ntiles, seed, blocky"""
+    names = list(ZOO_TEX_PLACEMENTS)
+    pairs = []
+    for k, c in enumerate(zoo_cases()):
+        mine = [names[k % len(names)]]
+        if c["name"] in ZOO_TEX_FULL_CROSS:
+            mine += [p for p in names if p != mine[0]]
+        pairs += [(c["name"], p) for p in mine]
+    return [dict(id=f"{name}-{p}", name=name, placement=p, ntiles=ZOO_TEX_TILES[n % len(ZOO_TEX_TILES)], seed=n,
+                 blocky=ZOO_TEX_BLOCKY[n % len(ZOO_TEX_BLOCKY)]) for n, (name, p) in enumerate(pairs)]
+
+
+def zoo_tex_sectors():
+    """narrow and odd sectors of the cases whose near ground the clipper cuts: (case name, first column, one past the
+    last).  In a sector a few columns wide a chunk of 256 pixels spans many rows, and a clipped triangle starts a run
+    on every one of them"""
+    zoo = {c["name"]: c for c in zoo_cases()}
+    out = []
+    for name in ("checker-zoom12", "checker-vertex360", "checker-near360", "max16-near360", "bowl-vertex360"):
+        W = zoo[name]["W"]
+        out += [(name, W // 2, W // 2 + 1), (name, W // 3, W // 3 + 17), (name, 5, 68), (name, 0, 64), (name, W - 65, W)]
+    out.append(("cliff-z005", 447, 512))
+    return out
+
+
+def zoo_tex_entry(name, placement="wrap"):
+    """the entry of zoo_tex_cases() for a zoo case: under `placement` where it has that one, else the one it has"""
+    mine = [e for e in zoo_tex_cases() if e["name"] == name]
+    return next((e for e in mine if e["placement"] == placement), mine[0])
+
+
+def zoo_tex_inputs(e, case=None):
+    """(texture parameters, texels) of an entry of zoo_tex_cases()"""
+    if case is None:
+        case = next(c for c in zoo_cases() if c["name"] == e["name"])
+    t = zoo_tex(case, e["placement"], e["ntiles"])
+    return t, hash_texture(t.tex_h, t.tex_w, seed=e["seed"], blocky=e["blocky"])
 
 
 # ---- .hgt tiles anywhere on Earth, with what real SRTM holds and tools/demgen.c does not write ----------------

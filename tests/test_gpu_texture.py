@@ -59,39 +59,6 @@ def test_textured_sector_tiles_the_panorama():
 
 # ---- through the reference's API: tiles from disk, caller-supplied mosaic, moves ----
 
-def _write_tiles(root, name, lowest_x, lowest_y, nx, ny, seed):
-    """zoom-12 map tiles as PNG files in the layout the reference reads
-    (dir_tiles/tiles_name/12/X/Y.png), in the PNG flavours tile servers emit; returns the
-    mosaic as the reference builds it: uint8[ny*256, nx*256, 3] B,G,R, southern row first"""
-    from PIL import Image
-    rng = np.random.default_rng(seed)
-    mosaic = np.zeros((ny * 256, nx * 256, 3), np.uint8)
-    highest_y = lowest_y + ny - 1
-    k = 0
-    for ty in range(lowest_y, lowest_y + ny):
-        for tx in range(lowest_x, lowest_x + nx):
-            yy, xx = np.mgrid[0:256, 0:256]
-            rgb = np.stack([(xx * 3 + tx * 40) % 256, (yy * 5 + ty * 17) % 256, (xx + yy + 31 * k) % 256], -1).astype(np.uint8)
-            rgb = (rgb.astype(int) + rng.integers(-20, 21, rgb.shape)).clip(0, 255).astype(np.uint8)
-            img = Image.fromarray(rgb, "RGB")
-            flavour = k % 4
-            if flavour == 1:            # palettised, as OSM's own tiles are (reference :339-352)
-                img = img.quantize(colors=200)
-                rgb = np.asarray(img.convert("RGB"))
-            elif flavour == 2:          # with an alpha channel, which is dropped
-                img = img.convert("RGBA")
-            elif flavour == 3:          # grey
-                img = img.convert("L")
-                rgb = np.repeat(np.asarray(img)[..., None], 3, -1)
-            d = root / name / "12" / str(tx)
-            d.mkdir(parents=True, exist_ok=True)
-            img.save(d / f"{ty}.png")
-            x0, y0 = (tx - lowest_x) * 256, (highest_y - ty) * 256
-            mosaic[y0:y0 + 256, x0:x0 + 256] = rgb[::-1, :, ::-1]      # bottom-up rows, B,G,R
-            k += 1
-    return mosaic
-
-
 def test_render_texture_through_the_api(tmp_path):
     import horizonator_amd
     R, W, H = 64, 640, 160
@@ -99,7 +66,7 @@ def test_render_texture_through_the_api(tmp_path):
     od = oracle.Dem(LAT, LON, d, radius_cells=R)
     m = od.mosaic()
     t = od.texture(LAT, LON)
-    texels = _write_tiles(tmp_path, "mapnik", t.lowest_x, t.lowest_y, t.ntiles_x, t.ntiles_y, 9)
+    texels = hzutil.write_map_tiles(tmp_path, "mapnik", t.lowest_x, t.lowest_y, t.ntiles_x, t.ntiles_y, 9)
 
     h = horizonator_amd.horizonator(LAT, LON, W, H, render_texture=True, dir_dems=d, dir_tiles=str(tmp_path),
                                     allow_downloads=False, render_radius_cells=R)

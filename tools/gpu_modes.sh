@@ -1,5 +1,5 @@
 #!/bin/bash
-# The GPU test suite once under each mode that runs DIFFERENT code from the default (about 1.5 minutes each on an MI355X;
+# The GPU test suite (tests/test_gpu_texture_zoo.py, the textured zoo, included) once under each mode that runs DIFFERENT code from the default (about 2 minutes each on an MI355X;
 # hz_options_t in include/hz_hip.h says what each switch does):
 #   one stream; one round / two rounds forced on every scene (two rounds on small scenes make the first round the longer
 #   one - that is how the conversion-waits-for-both-rounds bug of round 2 showed), with a short and a long reach;

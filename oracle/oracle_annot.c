@@ -5,8 +5,12 @@
  * they call (reference horizonator-lib.c:1053-1213).  PARITY UNPINNED by a run of
  * the reference: annotator.c needs cairo and libswscale, which this image lacks
  * (tests/caller_stubs holds stand-ins for LINKING the reference's CLI; a run
- * against stand-ins would pin nothing).  The device kernels are compared with this
- * file within 1e-6 degrees / 1e-3 pixels (tests/test_annot.py), not bit for bit.
+ * against stand-ins would pin nothing).  What stands in for such a run is a second
+ * statement of the same text, tests/naive_annot.py (NumPy scalars + glibc, sharing
+ * no code with this file): tests/test_naive_annot.py holds the two, and the
+ * library's host functions, to each other bit for bit.  The device kernels are
+ * compared with this file (tests/test_annot.py) and with naive_annot.py
+ * (tests/test_gpu_annot_zoo.py) for equality: every float and every flag the same.
  */
 #define _GNU_SOURCE
 #include <float.h>

@@ -203,6 +203,66 @@ class HipDev:
             setattr(tp, name, getattr(tex, name))
         return self.lib.hz_hip_set_texture(self.dev, C.byref(tp), None)
 
+    # ---- the draw and the readers of its framebuffer on their own: thin wrappers, return codes handed back -------------
+
+    def _view_tanel(self, view):
+        import oracle
+        v = hzlib.View()
+        for name, _ in hzlib.View._fields_:
+            setattr(v, name, getattr(view, name))
+        return v, np.ascontiguousarray(oracle.tanel(self.W, self.H, v.az_deg0, v.az_deg1), np.float32)
+
+    def last_error(self):
+        return self.lib.hz_hip_last_error().decode()
+
+    def set_options(self, **kw):
+        """hz_hip_set_options with some fields replaced, e.g. set_options(host_sectors=3, resolve_clears=0)"""
+        import ctypes as C
+        o = hzlib.Options()
+        assert self.lib.hz_hip_get_options(self.dev, C.byref(o)) == 0
+        for k, x in kw.items():
+            assert k in dict(hzlib.Options._fields_), k
+            setattr(o, k, int(x))
+        assert self.lib.hz_hip_set_options(self.dev, C.byref(o)) == 0, self.last_error()
+
+    def draw(self, view, col0=0, col1=None):
+        """hz_hip_set_sector + hz_hip_draw: the framebuffer the readers below read"""
+        import ctypes as C
+        assert self.lib.hz_hip_set_sector(self.dev, col0, self.W if col1 is None else col1) == 0, self.last_error()
+        v, _ = self._view_tanel(view)
+        assert self.lib.hz_hip_draw(self.dev, C.byref(v)) == 0, self.last_error()
+
+    def link_cells(self, view, sin_az, cos_az, cos_el, viewer_lat, cos_viewer_lat, viewer_lon, cell_w, cell_h, nx, ny, fill=12345.0):
+        """hz_hip_link_cells: (return code, lat, lon); the outputs are float32[max(ny,0), max(nx,0)] (one element where that
+        is empty) prefilled with `fill`, so that a refused call shows that it wrote nothing.  A table may be None"""
+        import ctypes as C
+        v, tanel = self._view_tanel(view)
+        shape = (ny, nx) if nx > 0 and ny > 0 else (1, 1)
+        lat, lon = np.full(shape, fill, np.float32), np.full(shape, fill, np.float32)
+        tabs = [None if t is None else np.ascontiguousarray(t, dt) for t, dt in ((sin_az, np.float32), (cos_az, np.float32), (cos_el, np.float64))]
+        rc = self.lib.hz_hip_link_cells(self.dev, C.byref(v), tanel.ctypes.data, *[None if t is None else t.ctypes.data for t in tabs],
+                                        viewer_lat, cos_viewer_lat, viewer_lon, cell_w, cell_h, nx, ny, lat.ctypes.data, lon.ctypes.data)
+        return rc, lat, lon
+
+    def poi(self, view, proj, cut_off_bottom_px, fill=77):
+        """hz_hip_poi_visibility on projected points float64[n,3] (x, y, range): (return code, visible, label_x, label_y),
+        the outputs prefilled with `fill`"""
+        import ctypes as C
+        v, tanel = self._view_tanel(view)
+        proj = np.ascontiguousarray(proj, np.float64).reshape(-1, 3)
+        n = len(proj)
+        vis, x, y = np.full(max(n, 1), fill, np.uint8), np.full(max(n, 1), fill, np.float32), np.full(max(n, 1), fill, np.float32)
+        rc = self.lib.hz_hip_poi_visibility(self.dev, C.byref(v), tanel.ctypes.data, cut_off_bottom_px, proj.ctypes.data, n,
+                                            vis.ctypes.data, x.ctypes.data, y.ctypes.data)
+        return rc, vis[:n], x[:n], y[:n]
+
+    def read_depth(self, x, y):
+        """hz_hip_read_depth: (return code, z24)"""
+        import ctypes as C
+        z = C.c_uint32(0xDEADBEEF)
+        rc = self.lib.hz_hip_read_depth(self.dev, int(x), int(y), C.byref(z))
+        return rc, z.value
+
     def render(self, view, col0=0, col1=None, tanel=None, want=("bgr", "ranges", "index", "z24")):
         """`view` is anything with the hz_view_t field names as attributes (e.g. oracle.OrcView);
         `want`: the outputs asked for (NULL goes in for the others), returned as a dict of those"""

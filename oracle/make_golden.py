@@ -365,6 +365,58 @@ def zoo_tex_checksum_fixtures():
         json.dump(out, f, indent=1, allow_nan=False)
 
 
+def shape_checksum_fixtures():
+    """image shapes at the kernels' size boundaries (hzutil.shape_cases: zoo grounds at 1x1 .. 70001x7 and 7x70001):
+    SHA-256 of the reference's draw of every case llvmpipe can draw (up to 16384 pixels a side), the terrain pixel count
+    of the oracle's draw for all of them.  A case on which the oracle differs from llvmpipe is not written: the GPU tests
+    take index and ranges from the oracle on its strength, and beyond 16384 pixels a side the oracle alone.  Likewise the
+    textured draws of hzutil.SHAPE_TEX_CASES.  Hashes, sizes and view values only, no images"""
+    import hashlib
+    import json
+    out = {}
+    cases = hzutil.shape_cases()
+    tex_seed = dict(hzutil.SHAPE_TEX_CASES)
+    assert set(tex_seed) <= {c["id"] for c in cases}
+    for c in cases:
+        m = hzutil.zoo_mosaic(c["family"], c["N"])
+        v = oracle.make_view(**c["view"])
+        W, H = c["W"], c["H"]
+        o = oracle.render(m, v, W, H, want=("bgr", "z24"))
+        e = {"name": c["name"], "N": c["N"], "W": W, "H": H,
+             "view": hzutil.zoo_view_json({k: float(np.float32(x)) for k, x in v.as_dict().items()}),
+             "mosaic_sha256": hashlib.sha256(m.tobytes()).hexdigest(),
+             "terrain_pixels": int((o["z24"] != 0xFFFFFF).sum())}
+        drawable = W <= hzutil.SHAPE_LLVMPIPE_MAX and H <= hzutil.SHAPE_LLVMPIPE_MAX
+        if drawable:
+            g = glsl_run.render(m, v, W, H)
+            if not (np.array_equal(o["bgr"], g["bgr"]) and np.array_equal(o["z24"], g["z24"])):
+                sys.exit(f"shape {c['id']}: the oracle's draw differs from llvmpipe's on "
+                         f"{int((o['bgr'] != g['bgr']).any(-1).sum())} pixels (depth: {int((o['z24'] != g['z24']).sum())}); nothing written")
+            e["bgr_sha256"] = hashlib.sha256(g["bgr"].tobytes()).hexdigest()
+            e["z24_sha256"] = hashlib.sha256(g["z24"].tobytes()).hexdigest()
+        if c["id"] in tex_seed:
+            t, texels = hzutil.shape_tex_inputs(c, tex_seed[c["id"]])
+            t = hzutil.orc_tex(t)
+            ot = oracle.render(m, v, W, H, tex=t, texels=texels, want=("bgr", "z24"))
+            if drawable:
+                gt = glsl_run.render_textured(m, v, W, H, t.as_glsl_job(), texels)
+                if not (np.array_equal(ot["bgr"], gt["bgr"]) and np.array_equal(ot["z24"], gt["z24"])):
+                    sys.exit(f"shape {c['id']}: the oracle's textured draw differs from llvmpipe's on "
+                             f"{int((ot['bgr'] != gt['bgr']).any(-1).sum())} pixels; nothing written")
+            e["tex_seed"] = tex_seed[c["id"]]
+            e["tex_bgr_sha256"] = hashlib.sha256(ot["bgr"].tobytes()).hexdigest()
+        out[c["id"]] = e
+        print(f"shape {c['id']}: terrain pixels {e['terrain_pixels']} of {W * H}{'' if drawable else ' (oracle only)'}", flush=True)
+    # conditions on the case list, judged on the oracle's draw: terrain in some case of every shape and in four cases of five
+    for W, H in sorted({(c["W"], c["H"]) for c in cases}):
+        assert any(out[c["id"]]["terrain_pixels"] for c in cases if (c["W"], c["H"]) == (W, H)), f"no terrain at {W}x{H}"
+    shown = sum(1 for e in out.values() if e["terrain_pixels"])
+    assert 5 * shown >= 4 * len(out), f"terrain in {shown} of {len(out)} cases only"
+    print(f"shapes: {len(out)} cases, terrain in {shown}")
+    with open(os.path.join(OUT, "shape_checksums.json"), "w") as f:
+        json.dump(out, f, indent=1, allow_nan=False)
+
+
 def raster_probe_fixture():
     """llvmpipe's fill rule and depth rounding on hand-made triangles (our own
     pass-through shaders; no reference code involved)"""
@@ -414,6 +466,9 @@ def main():
     if sys.argv[1:] == ["zootex"]:              # only tests/golden/zoo_tex_checksums.json
         zoo_tex_checksum_fixtures()
         return
+    if sys.argv[1:] == ["shapes"]:              # only tests/golden/shape_checksums.json
+        shape_checksum_fixtures()
+        return
     dem_fixtures()
     dem_world_fixtures()
     raster_probe_fixture()
@@ -437,6 +492,7 @@ def main():
     texture_fixtures()
     zoo_checksum_fixtures()
     zoo_tex_checksum_fixtures()
+    shape_checksum_fixtures()
 
 
 if __name__ == "__main__":

@@ -317,6 +317,15 @@ def assert_same_render(a, b, what=""):
                                      f"{a[k][tuple(bad[0])]} vs {b[k][tuple(bad[0])]}")
 
 
+def same_render(a, b, what=""):
+    """assert_same_render, with ranges that are NaN in the same places counted as equal: without a far clip
+    (zfar = inf) the reference's own range formula gives 0 * inf on terrain"""
+    if "ranges" in a and "ranges" in b:
+        assert np.array_equal(np.isnan(a["ranges"]), np.isnan(b["ranges"])), f"{what}: ranges are NaN in different places"
+    assert_same_render({k: np.nan_to_num(x, nan=-7.0) if k == "ranges" else x for k, x in a.items()},
+                       {k: np.nan_to_num(x, nan=-7.0) if k == "ranges" else x for k, x in b.items()}, what)
+
+
 # ---- the terrain zoo: hand-made ground, integer arithmetic only --------------
 
 def _zoo_hash(i, j, seed):
@@ -457,6 +466,96 @@ def zoo_cases():
                               degenerate=bool(r.get("degenerate", False))))
     assert len({c["name"] for c in cases}) == len(cases)
     return cases
+
+
+# ---- image shapes at the kernels' size boundaries: zoo grounds and views at other W x H --------------------
+
+# tiny images: narrower than the short cull's 64 columns, than one `touched` segment (256), than a tile of the coarse depth
+# (8 x 4, 32 x 16) or of the tile bins (64 x 64), lower than the host path's four bands of rows, narrower than its eight sectors
+SHAPES_TINY = ((1, 1), (1, 7), (7, 1), (2, 2), (3, 5), (4, 4), (5, 3), (15, 4), (16, 9), (63, 17), (64, 16), (65, 33),
+               (255, 3), (256, 4), (257, 5), (9, 300), (3, 2000), (16384, 4), (4, 16384))
+SHAPES_TINY_GROUNDS = ("coast-near360", "checker-near360", "spikes-zoom12", "cliff-arctic90")
+# ... the boundaries that list misses: one row of a whole segment, the coarse-depth tiles (32 x 16) from both sides, the
+# tile bins (64 x 64), two segments in fewer rows than bands, a host blob's 2048 columns from both sides
+SHAPES_EDGE = ((64, 1), (31, 15), (32, 16), (33, 17), (65, 65), (512, 2), (2047, 5), (2048, 5), (2049, 5))
+# wide images: the packed 16-bit pixel boxes of the short cull end at 65535 columns, hz_hip_pack_sparse at 65536
+SHAPES_WIDE = ((65535, 8), (65536, 8), (65537, 9), (70001, 7))
+SHAPES_WIDE_GROUNDS = ("coast-near360", "spikes-near360", "cliff-near360", "bowl-near360", "stairs-near360", "checker-vertex360",
+                       "spikes-high_wrap")
+# tall images: a blob's 16-bit row field ends at 65535 rows; the terrain lies around row H/2: 32768 at H = 65536, the sign
+# bit of a 16-bit row, and beyond 65535 itself at H = 140001.  The azimuth extents are replaced: in a span as narrow as the
+# aspect asks for every cell crosses a quarter of the image
+SHAPES_TALL = ((8, 65536), (7, 70001), (33, 65535), (8, 140001))
+SHAPES_TALL_GROUNDS = ("spikes-corner90", "coast-corner90", "stairs-corner90", "cliff-sky", "checker-sky", "spikes-high_wrap",
+                       "bowl-high_wrap")
+SHAPES_TALL_AZ = (10.0, 14.0)
+# The short cull itself (mr_simple_cull: rows whose 64 vertices all lie inside the view volume) never runs on the shapes above:
+# seven rows of a 70001-column panorama are 0.04 degrees of elevation, and four degrees of azimuth hold no whole strip.
+# 4 Mpix images that give it rows to run on, on both sides of its limits.  Wide: a viewer two metres above level ground
+# (the zoo case's viewer_z replaced), so that the ground beyond 650 m lies within the 0.35 degrees of 64 rows.  Tall: the
+# zoo cases' own 360 degrees in 64 columns - every vertex is inside, the terrain lies in a few rows around row 32768
+SHAPES_CULL_WIDE = ((65535, 64), (65536, 64), (65537, 63))
+SHAPES_CULL_WIDE_GROUNDS = (("flat0-near360", 2.0), ("plateau-near360", 1236.0), ("stairs-near360", 202.0))
+SHAPES_CULL_TALL = ((64, 65535), (64, 65536), (63, 66000))
+SHAPES_CULL_TALL_GROUNDS = ("coast-near360", "spikes-near360", "bowl-near360")
+SHAPE_LLVMPIPE_MAX = 16384              # llvmpipe draws no more pixels a side: larger shapes are held to the oracle alone
+
+
+def _shape_sector(W, k):
+    """the sector of the k-th case of a shape: in turn one column at column 0, the last column alone, a width that is no
+    multiple of 4 from a start that is one, a start that is no multiple of 4; from 65537 columns on also six columns
+    across column 65536 and the last three.  Images of fewer than four columns: the whole image"""
+    if W < 4:
+        return 0, W
+    c_odd = min(W - 2, (W // 5) | 1)
+    kinds = [(0, 1), (W - 1, W), (W // 3 // 4 * 4, W // 3 // 4 * 4 + max(1, min(W - W // 3 // 4 * 4, (W // 2) | 1))),
+             (c_odd, min(W, c_odd + max(4, W // 2 // 4 * 4)))]
+    if W >= 65537:
+        kinds = [(65533, min(W, 65539)), (W - 3, W)] + kinds
+    c0, c1 = kinds[k % len(kinds)]
+    assert 0 <= c0 < c1 <= W
+    return c0, c1
+
+
+def shape_cases():
+    """zoo grounds and views at image shapes next to the size rules of the kernels, deterministic: dicts with id, name (the
+    zoo case's), family, N, W, H, view (the zoo case's with aspect = float32(W)/float32(H); for the tall shapes with the
+    azimuth extents of SHAPES_TALL_AZ, for the wide shapes of the short cull with another viewer_z), az (those extents, or
+    None), c0, c1 (a sector: _shape_sector) and kind"""
+    f32 = np.float32
+    zoo = {c["name"]: c for c in zoo_cases()}
+    cases = []
+    for kind, shapes, grounds, az in (("tiny", SHAPES_TINY, SHAPES_TINY_GROUNDS, None), ("edge", SHAPES_EDGE, SHAPES_TINY_GROUNDS, None),
+                                      ("wide", SHAPES_WIDE, SHAPES_WIDE_GROUNDS, None), ("tall", SHAPES_TALL, SHAPES_TALL_GROUNDS, SHAPES_TALL_AZ),
+                                      ("cull", SHAPES_CULL_WIDE, SHAPES_CULL_WIDE_GROUNDS, None),
+                                      ("cull", SHAPES_CULL_TALL, SHAPES_CULL_TALL_GROUNDS, None)):
+        for W, H in shapes:
+            for k, ground in enumerate(grounds):
+                name, vz = ground if isinstance(ground, tuple) else (ground, None)
+                z = zoo[name]
+                view = dict(z["view"])
+                view["aspect"] = float(f32(W) / f32(H))
+                if az is not None:
+                    view["az_deg0"], view["az_deg1"] = float(f32(az[0])), float(f32(az[1]))
+                if vz is not None:
+                    view["viewer_z"] = float(f32(vz))
+                c0, c1 = _shape_sector(W, k)
+                cases.append(dict(id=f"{W}x{H}-{name}" + ("" if vz is None else "-vz%g" % vz), name=name, family=z["family"], N=z["N"],
+                                  W=W, H=H, view=view, az=None if az is None else [float(az[0]), float(az[1])], c0=c0, c1=c1, kind=kind))
+    assert len({c["id"] for c in cases}) == len(cases)
+    return cases
+
+
+# the textured resolve on five of the shapes: (shape case, texture seed); the texture is zoo_tex(case, "wrap", (3, 2))
+# over hash_texture(512, 768, seed)
+SHAPE_TEX_CASES = (("1x1-spikes-zoom12", 21), ("7x1-coast-near360", 22), ("255x3-coast-near360", 23), ("257x5-spikes-zoom12", 24),
+                   ("70001x7-checker-vertex360", 25))
+
+
+def shape_tex_inputs(case, seed):
+    """(texture parameters, texels) of a textured shape case"""
+    t = zoo_tex(case, "wrap", (3, 2))
+    return t, hash_texture(t.tex_h, t.tex_w, seed=seed)
 
 
 # ---- texture placements for the zoo: where the DEM window lies on the mosaic of map tiles -----------------

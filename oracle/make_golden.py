@@ -417,6 +417,41 @@ def shape_checksum_fixtures():
         json.dump(out, f, indent=1, allow_nan=False)
 
 
+def edge_checksum_fixtures():
+    """viewer positions at the edges of the grid and of its strips, and DEM sizes around whole strips (hzutil.edge_cases):
+    per case the view values, the mosaic's hash, the terrain pixel count of the oracle's draw and the SHA-256 of what the
+    reference's shaders drew on llvmpipe.  Nothing is written if the oracle's draw differs from llvmpipe's on any case: the
+    GPU tests take index and ranges from the oracle on its strength.  Hashes and numbers only"""
+    import hashlib
+    import json
+    out = {}
+    cases = hzutil.edge_cases()
+    for c in cases:
+        m = hzutil.zoo_mosaic(c["family"], c["N"])
+        v = oracle.make_view(**c["view"])
+        W, H = c["W"], c["H"]
+        o = oracle.render(m, v, W, H, want=("bgr", "z24"))
+        g = glsl_run.render(m, v, W, H)
+        if not (np.array_equal(o["bgr"], g["bgr"]) and np.array_equal(o["z24"], g["z24"])):
+            sys.exit(f"edge {c['id']}: the oracle's draw differs from llvmpipe's on "
+                     f"{int((o['bgr'] != g['bgr']).any(-1).sum())} pixels (depth: {int((o['z24'] != g['z24']).sum())}); nothing written")
+        out[c["id"]] = {"family": c["family"], "recipe": c["recipe"], "N": c["N"], "W": W, "H": H, "kind": c["kind"], "empty": c["empty"],
+                        "view": hzutil.zoo_view_json({k: float(np.float32(x)) for k, x in v.as_dict().items()}),
+                        "mosaic_sha256": hashlib.sha256(m.tobytes()).hexdigest(),
+                        "terrain_pixels": int((o["z24"] != 0xFFFFFF).sum()),
+                        "bgr_sha256": hashlib.sha256(g["bgr"].tobytes()).hexdigest(),
+                        "z24_sha256": hashlib.sha256(g["z24"].tobytes()).hexdigest()}
+        print(f"edge {c['id']}: terrain pixels {out[c['id']]['terrain_pixels']} of {W * H}", flush=True)
+    # conditions on the case list, judged on the oracle's draw
+    for c in cases:
+        assert (out[c["id"]]["terrain_pixels"] == 0) == c["empty"], f"{c['id']}: {out[c['id']]['terrain_pixels']} terrain pixels, empty={c['empty']}"
+    empty = sum(c["empty"] for c in cases)
+    assert 8 * empty <= len(cases), f"{empty} of {len(cases)} cases are empty"
+    print(f"edges: {len(cases)} cases, terrain in {len(cases) - empty}, empty {empty}")
+    with open(os.path.join(OUT, "edge_checksums.json"), "w") as f:
+        json.dump(out, f, indent=1, allow_nan=False)
+
+
 def raster_probe_fixture():
     """llvmpipe's fill rule and depth rounding on hand-made triangles (our own
     pass-through shaders; no reference code involved)"""
@@ -469,6 +504,9 @@ def main():
     if sys.argv[1:] == ["shapes"]:              # only tests/golden/shape_checksums.json
         shape_checksum_fixtures()
         return
+    if sys.argv[1:] == ["edges"]:               # only tests/golden/edge_checksums.json
+        edge_checksum_fixtures()
+        return
     dem_fixtures()
     dem_world_fixtures()
     raster_probe_fixture()
@@ -493,6 +531,7 @@ def main():
     zoo_checksum_fixtures()
     zoo_tex_checksum_fixtures()
     shape_checksum_fixtures()
+    edge_checksum_fixtures()
 
 
 if __name__ == "__main__":

@@ -558,6 +558,154 @@ def shape_tex_inputs(case, seed):
     return t, hash_texture(t.tex_h, t.tex_w, seed=seed)
 
 
+# ---- viewer positions at the grid's edges and odd DEM sizes: zoo grounds, zoo views with the viewer moved ----------------
+
+EDGE_GROUNDS = ("coast", "spikes", "checker", "stairs", "border_minus1", "bowl")
+EDGE_N, EDGE_W, EDGE_H = 128, 640, 160          # 127 cells: strips end at vertex columns 63 and 126, the last strip has one cell
+MR_COLS = 63                                    # (hz_types.h: cells of a strip)
+_P17, _P36, _P40 = 2.0 ** -17, 2.0 ** -36, 2.0 ** -40
+# metres per cell as the transform forms it (hz_num.h: hz_north; hz_east times cos(latitude)): 20015088 / cells per degree / 180
+EDGE_M_PER_CELL = {1200: 92.66244, 3600: 30.88748}
+# (tag, i, j, kind, recipe, overrides of the recipe).  kind: "vertex" = a zero east or north offset at some vertex, "tiny" =
+# an offset below hz_fast.h's HZF_LO = 2^-30 that is not zero, "in" = neither, "out" = the viewer outside the grid.
+# 2^-40 cells are 92.66 * 2^-40 = 8.4e-11 m north (6.9e-11 m east at 34.4 degrees); 2^-36 cells of 1/3600 degree are
+# 30.89 * 2^-36 = 4.5e-10 m north - with 1/1200 degree they would be 1.35e-9 m, above 2^-30 = 9.3e-10: that position is
+# drawn with vertex360's cells.  tests/test_oracle_golden.py asserts the products
+_EDGE_POSITIONS = (
+    # on a strip boundary
+    ("i63", 63.0, 40.37, "vertex", "near360", {}),
+    ("i63-", 63.0 - _P17, 40.37, "in", "near360", {}),
+    ("i63+", 63.0 + _P17, 40.37, "in", "near360", {}),
+    ("i63_2500m", 63.0, 40.37, "vertex", "high_wrap", {}),
+    ("i126_j126", 126.0, 126.0, "vertex", "near360", {}),
+    ("i126_j0", 126.0, 0.0, "vertex", "near360", {}),          # row0[0..3] = 0: the viewer's row is a segment's first
+    ("i126_j127", 126.0, 127.0, "vertex", "near360", {}),      # row0[4..7] = 127: ... its last
+    ("i126_j4", 126.0, 4.0, "vertex", "near360", {}),          # row0[3] = 0, two rows a segment: last of [2,4], first of [4,6]
+    ("i62.5_j63", 62.5, 63.0, "vertex", "near360", {}),        # n = 0 only
+    # on the border, in the last and the first cell
+    ("sw_corner", 0.0, 0.0, "vertex", "near360", {}),
+    ("w_border", 0.0, 64.29, "vertex", "near360", {}),
+    ("s_border", 64.37, 0.0, "vertex", "near360", {}),
+    ("ne_corner", 127.0, 127.0, "vertex", "near360", {}),
+    ("e_border", 127.0, 30.5, "vertex", "near360", {}),
+    ("last_cell", 126.5, 126.5, "in", "near360", {}),
+    ("first_cell", 0.5, 0.5, "in", "near360", {}),
+    # tiny offsets
+    ("tiny_ij", _P40, _P40, "tiny", "near360", {}),
+    ("tiny_i", _P40, 64.29, "tiny", "near360", {}),
+    ("tiny_j", 64.37, _P36, "tiny", "vertex360", {}),
+    # just outside
+    ("out_w", -0.5, 64.29, "out", "near360", {}),
+    ("out_sw1", -1.0, -1.0, "out", "near360", {}),
+    ("out_sw", -3.7, -2.2, "out", "near360", {}),
+    ("out_sw_2500m", -3.7, -2.2, "out", "high_wrap", {}),
+    ("out_e", 130.25, 64.6, "out", "near360", {}),
+    ("out_n", 64.4, 131.0, "out", "near360", {}),
+    ("out_ne", 128.0, 128.0, "out", "near360", {}),
+    # well outside, the grid within zfar: 360 degrees, 90 degrees at the grid, 90 degrees away from it (empty by design)
+    ("far_w_360", -200.3, 64.29, "out", "near360", dict(z=(100.0, 60000.0))),
+    ("far_w_at", -200.3, 64.29, "out", "near360", dict(z=(100.0, 60000.0), az=(45.0, 135.0))),
+    ("far_w_away", -200.3, 64.29, "out", "near360", dict(z=(100.0, 60000.0), az=(225.0, 315.0), empty=True)),
+    ("far_n_360", 64.37, 400.2, "out", "near360", dict(z=(100.0, 60000.0))),
+    ("far_n_at", 64.37, 400.2, "out", "near360", dict(z=(100.0, 60000.0), az=(135.0, 225.0))),
+    ("far_n_away", 64.37, 400.2, "out", "near360", dict(z=(100.0, 60000.0), az=(-45.0, 45.0), empty=True)),
+    # the whole grid beyond zfar
+    ("beyond_zfar", -2000.0, -2000.0, "out", "near360", dict(empty=True)),
+    # extents (170, 530) put the image's seam at azimuth 170: seen from the south the grid lies around azimuth 0, in the
+    # middle of the image; seen from the north it lies around azimuth 180 and straddles the seam
+    ("seam_from_s", 60.2, -30.4, "out", "near360", dict(az=(170.0, 530.0))),
+    ("seam_from_n", 70.3, 160.6, "out", "near360", dict(az=(170.0, 530.0))),
+)
+EDGE_SIZES = (2, 3, 4, 5, 63, 64, 65, 66, 126, 127, 128, 129, 190, 191)
+EDGE_SIZE_GROUNDS = ("spikes", "checker", "plateau")
+EDGE_SIZE_W, EDGE_SIZE_H = 320, 80
+
+
+# Dropped from the list: the one case on which the oracle's draw differs from llvmpipe's, in one pixel.  Triangle 11005 there is
+# a sliver 68 pixels tall whose area is positive in the snapped 1/256-pixel positions (5544/65536 px^2: llvmpipe's rasteriser
+# and the oracle draw it) and negative in the unsnapped float positions.  Mesa's draw module culls by the float area, but only
+# the triangles of a batch that holds a clipped vertex: drawn alone, or with an unclipped triangle, llvmpipe fills the pixel;
+# with a triangle across the image border in the same call it does not.  GL leaves the precision of the facing test to the
+# implementation, and which triangles share a batch is nothing the oracle can restate
+EDGE_DROPPED = ("i126_j127-checker",)
+
+
+def _edge_above(m, ci, cj):
+    """10 m above the highest of the four samples around the viewer, as the zoo's "above"; samples outside the window count
+    as -1 (what the DEM reader returns there)"""
+    N = m.shape[0]
+    i0, j0 = int(np.floor(ci)), int(np.floor(cj))
+    z = [int(m[j, i]) if 0 <= i < N and 0 <= j < N else -1 for j in (j0, j0 + 1) for i in (i0, i0 + 1)]
+    return float(max(z)) + 10.0
+
+
+def _edge_case(cid, family, recipe, over, N, W, H, ci, cj, kind, k):
+    f32 = np.float32
+    r = dict(_ZOO_VIEWS[recipe]); r.update(over)
+    ci, cj = f32(ci), f32(cj)
+    vz = r["vz"]
+    if vz == "above":
+        vz = _edge_above(zoo_mosaic(family, N), ci, cj)
+    zc = r.get("zc", r["z"])
+    view = dict(viewer_cell_i=ci, viewer_cell_j=cj, viewer_z=f32(vz), cos_viewer_lat=f32(_ZOO_COS[r["lat"]]),
+                deg_per_cell=f32(1.0) / f32(r["cpd"]), az_deg0=f32(r["az"][0]), az_deg1=f32(r["az"][1]),
+                aspect=f32(W) / f32(H), znear=f32(r["z"][0]), zfar=f32(r["z"][1]),
+                znear_color=f32(zc[0]), zfar_color=f32(zc[1]))
+    c0, c1 = (W // 5 + k % 97, W // 5 + k % 97 + W // 3) if k % 2 else (0, W)
+    return dict(id=cid, family=family, recipe=recipe, lat=r["lat"], cpd=r["cpd"], N=N, W=W, H=H, kind=kind,
+                view={n: float(x) for n, x in view.items()}, c0=c0, c1=c1, empty=bool(r.get("empty", False)))
+
+
+def edge_cases():
+    """viewer positions at the edges of the grid and of its 63-cell strips, and DEM sizes around whole strips, deterministic:
+    dicts with id, family, recipe, N, W, H, view (float32-representable floats), kind (see _EDGE_POSITIONS; the sizes: "size"),
+    pos (the position's tag), c0, c1 (a sector on every other case) and empty (no terrain by design).  Every position on
+    N = 128 under one of EDGE_GROUNDS in rotation; every N of EDGE_SIZES from three places, each under one of EDGE_SIZE_GROUNDS in rotation"""
+    f32 = np.float32
+    cases = []
+    for n, (tag, ci, cj, kind, recipe, over) in enumerate(_EDGE_POSITIONS):
+        # (one ground per position, in rotation: under three each - the cross the list began with - the GPU tests on this list
+        # took a third of the suite's time before them; the decisions these positions are for depend on where the viewer
+        # stands, not on the heights)
+        grounds = [EDGE_GROUNDS[(n + t) % len(EDGE_GROUNDS)] for t in range(2)]
+        grounds = [g for g in grounds if f"{tag}-{g}" not in EDGE_DROPPED][:1]
+        for family in grounds:
+            if family == "stairs" and cj > EDGE_N - 1:          # (the stairs climb northwards: from the north, 10 m up, only their back)
+                family = "coast"
+            c = _edge_case(f"{tag}-{family}", family, recipe, over, EDGE_N, EDGE_W, EDGE_H, ci, cj, kind, len(cases))
+            c["pos"] = tag
+            cases.append(c)
+    for N in EDGE_SIZES:
+        lo, hi = f32(0), f32(N - 1)
+        places = (("mid", min(max(f32(N // 2) + f32(0.37), lo), hi), min(max(f32(N // 2) - f32(0.29), lo), hi)),
+                  ("corner", f32(0), f32(0)), ("outside", f32(-1.5), f32(N) + f32(0.5)))
+        for p, (tag, ci, cj) in enumerate(places):
+            for family in (EDGE_SIZE_GROUNDS[(EDGE_SIZES.index(N) + p) % len(EDGE_SIZE_GROUNDS)],):     # (one ground per place, in rotation)
+                # (from outside: above the highest sample of the grid - 10 m above the -1 around it is below the ground)
+                over = dict(vz=float(zoo_mosaic(family, N).max()) + 10.0) if tag == "outside" else {}
+                if N <= 5:                                      # (the whole grid lies within near360's near clip of 100 m)
+                    over["z"] = (1.0, 40000.0)
+                if N == 2 and tag != "outside":                 # (seen from inside it, the one cell spans a quarter of the image or more:
+                    over["empty"] = True                        #  the reference drops both triangles)
+                c = _edge_case(f"N{N}_{tag}-{family}", family, "near360", over, N, EDGE_SIZE_W, EDGE_SIZE_H, ci, cj, "size", len(cases))
+                c["pos"] = tag
+                cases.append(c)
+    assert len({c["id"] for c in cases}) == len(cases)
+    return cases
+
+
+def edge_offsets(c):
+    """the east and north offsets of every vertex column and row of an edge case from the viewer, in metres, as float32
+    arithmetic forms them (hz_num.h: hz_east, hz_north): what hz_fast.h's range test sees"""
+    f32 = np.float32
+    v = c["view"]
+    k = f32(20015088.0)
+    fi = np.arange(c["N"], dtype=f32)
+    e = (fi - f32(v["viewer_cell_i"])) * k * f32(v["deg_per_cell"]) / f32(180.0) * f32(v["cos_viewer_lat"])
+    n = (fi - f32(v["viewer_cell_j"])) * k * f32(v["deg_per_cell"]) / f32(180.0)
+    return e.astype(f32), n.astype(f32)
+
+
 # ---- texture placements for the zoo: where the DEM window lies on the mosaic of map tiles -----------------
 
 # placement -> s at the window's west and east edge, t over one window height of latitude, and the curvature

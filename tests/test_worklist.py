@@ -137,3 +137,73 @@ def test_full_circle_launches_the_grid():
     assert n > 0                                    # a 45 degree view: only the strips behind it
     nsx = (600 - 1 + MR_COLS - 1) // MR_COLS
     assert n < 0.6 * nsx * len({(int(jb), int(je)) for _, jb, je in items}) + 50
+
+
+# ---- viewers on the border of the grid and outside it, rays along the axes, spans around 180 degrees ----------------
+
+EDGE_VIEWERS = (("sw_corner", 0.0, 0.0), ("ne_corner", 1.0, 1.0), ("w_border", 0.0, 0.37), ("e_border", 1.0, 0.61), ("s_border", 0.43, 0.0),
+                ("n_border", 0.58, 1.0), ("out_w", -0.5, 0.3), ("out_e", 1.5, 0.7), ("out_s", 0.4, -0.5), ("out_n", 0.6, 1.5),
+                ("out_sw", -0.1, -0.1), ("out_ne", 1.2, 1.3))
+EDGE_AZ0 = (0.0, 90.0, 180.0, -90.0, 270.0, 37.5)
+# of these the parent of the commit that added them misses the length bound n <= needed + 2*len(segs) + 8 (listed: none)
+EDGE_OVER_THE_BOUND = ()
+
+
+def _edge_spans(az0):
+    a180 = np.float32(az0) + np.float32(180.0)
+    return ((az0 + 180.0, "180"), (float(np.nextafter(a180, np.float32(1e9))), "180+ulp"), (az0 + 359.9, "359.9"), (az0 + 45.0, "45"))
+
+
+@pytest.mark.parametrize("lat", [0.0, 80.0])
+@pytest.mark.parametrize("N", [64, 65, 127, 128])
+@pytest.mark.parametrize("viewer", EDGE_VIEWERS, ids=lambda t: t[0])
+def test_every_strip_is_listed_for_viewers_on_the_border_and_outside(viewer, N, lat):
+    """the superset requirement where hz_plan.cpp takes special cases: the patch that holds the viewer and the wedge's apex
+    with the viewer on the border; every band on one side of the viewer (outside the grid: (-0.5 .. 1.5) N); rays along the
+    axes (az0 a multiple of 90 degrees: fabs(c) < 1e-12); wedges of exactly 180 degrees, one float32 ulp more (two convex
+    halves) and 359.9; latitudes 0 and 80; grids of one and two whole strips and one cell more or less"""
+    tag, fi, fj = viewer
+    W, H = 1000, 250
+    worst = 0
+    for az0 in EDGE_AZ0:
+        for az1, span in _edge_spans(az0):
+            v = hzlib.View()
+            v.viewer_cell_i, v.viewer_cell_j = fi * (N - 1), fj * (N - 1)
+            v.viewer_z = 1500.0
+            v.cos_viewer_lat = float(np.cos(np.radians(lat)))
+            v.deg_per_cell = 1.0 / 1200.0
+            v.az_deg0, v.az_deg1 = az0, az1
+            v.aspect = W / H
+            v.znear, v.zfar = 100.0, 600000.0
+            v.znear_color, v.zfar_color = 100.0, 600000.0
+            x = _pixel_x(v, N, W)
+            for G in (1, 3):
+                edges = np.linspace(0, W, G + 1).astype(int)
+                for g in range(G):
+                    c0, c1 = int(edges[g]), int(edges[g + 1])
+                    n, items = _listed(N, W, H, v, c0, c1, 0)
+                    if n < 0:
+                        assert G == 1 and span == "359.9"      # (nearly) the full circle: the grid is launched
+                        continue
+                    assert n == len(items)
+                    _, every = _listed(N, W, H, v, c0, c1, 256)
+                    segs = sorted({(int(jb), int(je)) for _, jb, je in every})
+                    got = {(int(sx), int(jb), int(je)) for sx, jb, je in items}
+                    assert got <= {tuple(int(t) for t in r) for r in every}
+                    inside = (x >= c0 - 1.0) & (x <= c1 + 1.0)
+                    nsx = (N - 1 + MR_COLS - 1) // MR_COLS
+                    needed = 0
+                    for jb, je in segs:
+                        rows = inside[jb:je + 1]
+                        for sx in range(nsx):
+                            i0 = sx * MR_COLS
+                            if rows[:, i0:min(i0 + MR_COLS, N - 1) + 1].any():
+                                needed += 1
+                                assert (sx, jb, je) in got, (tag, N, lat, az0, span, G, g, sx, jb, je)
+                    excess = n - (needed + 2 * len(segs) + 8)
+                    if (tag, N, lat) in EDGE_OVER_THE_BOUND:
+                        worst = max(worst, excess)
+                    else:
+                        assert excess <= 0, (tag, N, lat, az0, span, G, g, n, needed, len(segs))
+    if (tag, N, lat) in EDGE_OVER_THE_BOUND:
+        print(f"work list {tag} N={N} lat={lat}: largest excess over the length bound {worst}")
